@@ -1,6 +1,7 @@
 """Benchmark: client-images/sec/node of the federated hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config KT]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config KT] [--dump-outputs DIR]
+    python bench.py --full ...
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one federated round over synthetic CIFAR/MNIST-shaped data
@@ -10,7 +11,11 @@ config has it, then FedAvg (RCCL all-reduce across ranks).  value =
 sum over ranks of samples_processed / max-over-ranks wall time of the K timed
 rounds.  Weak scaling: each GPU hosts the config's clients-per-GPU.
 
-Also reported (one JSON line):
+A plain run sets up, runs W warm-up rounds, times the K rounds, writes the last timed
+round's outputs when --dump-outputs is given (dump_outputs below) and prints the one JSON
+line.  Everything else is measured only with --full.
+
+Also reported with --full (on the same JSON line):
   roofline      the dominant conv launch shape, every launch of it timed live by the
                 kernel's own wall-clock stamps over a stretch of rounds identical to the
                 timed ones (run right after them): algorithmic FLOPs per launch / average
@@ -571,6 +576,45 @@ def timed_roofline(tag, inst_row, timed, steps, peak, workload):
     return r
 
 
+DUMP_MAX_BYTES = 60 << 20   # --dump-outputs: array bytes of one run (files: under 64 MB)
+
+
+def round_outputs(global_flat, global_bufs, metrics, client_params=None):
+    """What a caller of the timed path holds after a round, as named tensors: the new global
+    model (parameter vector, BN running statistics) — or, for the per-client DP-SGD round,
+    every client's trained row — and each client's training loss / accuracy / sample count."""
+    out = {}
+    if global_flat is not None:
+        out["global_params"] = global_flat
+    if global_bufs is not None:
+        out["global_buffers"] = global_bufs
+    if client_params is not None:
+        out["client_params"] = client_params
+    out["client_loss"] = torch.tensor([m.loss for m in metrics], dtype=torch.float64)
+    out["client_accuracy"] = torch.tensor([m.accuracy for m in metrics], dtype=torch.float64)
+    out["client_samples"] = torch.tensor([m.samples_processed for m in metrics],
+                                         dtype=torch.float64)
+    return out
+
+
+def dump_outputs(path, tensors):
+    """--dump-outputs: <path>/<name>.npy per tensor, float32 / float64, DUMP_MAX_BYTES in all.
+    An array that would not fit its even share of the budget is written as a fixed sample of
+    its flattened elements (sorted indices from numpy's default_rng(0): the same elements in
+    every run and every build)."""
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(1, len(tensors))
+    for name, t in tensors.items():
+        a = t.detach().cpu().numpy()
+        if a.dtype not in (np.float32, np.float64):
+            a = a.astype(np.float64)
+        keep = share // a.itemsize
+        if a.size > keep:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, size=keep, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(a))
+
+
 _MAPS_THREAD = None
 
 
@@ -599,10 +643,11 @@ def dump_maps_periodically(path, period=0.1):
     _MAPS_THREAD.start()
 
 
-def run_config(key, args, world, rank, dev, steps, warmup, rtt=False, cpu=True):
+def run_config(key, args, world, rank, dev, steps, warmup, rtt=False, cpu=True, dump=None):
     """Measure one BASELINE config: warmup rounds, `steps` timed rounds (barrier +
-    synchronize on both sides, max over ranks), then one instrumented round.  Returns the
-    rank-0 result dict (None on other ranks)."""
+    synchronize on both sides, max over ranks); with --full also one instrumented round and
+    the roofline stretch.  dump: directory for the last timed round's outputs (rank 0).
+    Returns the rank-0 result dict (None on other ranks)."""
     cfg = CONFIGS[key]
     labels, train = build_clients(cfg, world, strong=args.strong)
     C = len(train)
@@ -621,7 +666,8 @@ def run_config(key, args, world, rank, dev, steps, warmup, rtt=False, cpu=True):
         algo, ratio = cfg["compression"]
         comp = CompressionConfig(algorithm=algo, sparsity_ratio=ratio)
     rr = RankRound(template, train, mine, epochs=cfg["epochs"], device=dev, dp=dp,
-                   lanes=args.lanes, transform=tf, compression=comp, exact=args.exact_fedavg)
+                   lanes=args.lanes, transform=tf, compression=comp, exact=args.exact_fedavg,
+                   dp_seed=0 if args.dump_outputs else None)  # dumps compare run to run
     data, lab, offs = make_rank_data(cfg, train, rr.slots, dev, rank, raw=raw)
     total_images = cfg["epochs"] * sum(train)
 
@@ -646,7 +692,7 @@ def run_config(key, args, world, rank, dev, steps, warmup, rtt=False, cpu=True):
     inst = buckets = rows = stamps = None
     peak = FP32_MFMA_PEAK_TFLOPS
     ridge = peak * 1e12 / (HBM_PEAK_GBS * 1e9)
-    if not args.no_instances:
+    if args.full and not args.no_instances:
         ops.PROBE.reset()
         ops.PROBE.tag, ops.PROBE.enabled = "*", True
         rr.run(data, lab, offs, args.opt, args.lr, seed=999, generator=gen, serialize_lanes=True)
@@ -660,13 +706,17 @@ def run_config(key, args, world, rank, dev, steps, warmup, rtt=False, cpu=True):
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    metrics = None
     for s in range(steps):
-        rr.run(data, lab, offs, args.opt, args.lr, seed=100 + s, generator=gen)
+        metrics = rr.run(data, lab, offs, args.opt, args.lr, seed=100 + s, generator=gen)
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if dump and rank == 0 and metrics is not None:
+        dump_outputs(dump, round_outputs(rr.global_flat, rr.global_bufs if rr.Q else None,
+                                         metrics))
     timed = None
     if stamps is not None:
         # r06: the roofline shape's launch stamps run over a second stretch of the same rounds
@@ -749,8 +799,9 @@ def run_config(key, args, world, rank, dev, steps, warmup, rtt=False, cpu=True):
     # the host-CPU legs (oracle rounds-to-target, CPU baseline) run after every timed GPU
     # leg of the process (host_legs): their torch CPU thread pool would otherwise still be
     # spinning while a later config's rounds are issued from the host
-    out["_host"] = (cfg, [train[k] for k in rr.slots], world == 1 and rtt and args.rounds_target > 0,
-                    world == 1 and cpu and not args.no_cpu_baseline)
+    out["_host"] = (cfg, [train[k] for k in rr.slots],
+                    args.full and world == 1 and rtt and args.rounds_target > 0,
+                    args.full and world == 1 and cpu and not args.no_cpu_baseline)
     del rr, data, lab
     torch.cuda.empty_cache()
     return out
@@ -767,7 +818,7 @@ def host_legs(out, args, dev):
     return out
 
 
-def run_dpsgd(args, dev, steps, warmup):
+def run_dpsgd(args, dev, steps, warmup, dump=None):
     """`--config K2-dpsgd`: the K2 workload (SimpleCNN, 32 Dirichlet(0.5) clients, one
     local epoch) trained with per-sample DP-SGD (north_star extension, not in the
     reference): every step clips each image's gradient to C = 1 — linear layers by the
@@ -788,7 +839,8 @@ def run_dpsgd(args, dev, steps, warmup):
     model = hm.ModelFactory.create_model(cfg["model"], **cfg["kw"]).to(dev)
     eng = LanedTrainer(model, [math.ceil(n / 32) for n in sizes], batch=32, device=dev,
                        lanes=args.lanes,
-                       dpsgd=DPSGDConfig(max_grad_norm=1.0, epsilon=1.0, delta=1e-5))
+                       dpsgd=DPSGDConfig(max_grad_norm=1.0, epsilon=1.0, delta=1e-5,
+                                         seed=0 if dump else None))  # dumps compare run to run
     for k in range(len(sizes)):
         eng.load_module_state(k, model)
     g = torch.Generator(device=dev).manual_seed(1000)
@@ -801,23 +853,18 @@ def run_dpsgd(args, dev, steps, warmup):
     plans = [eng.make_plan(sizes, 1, generator=gen) for _ in range(steps)]
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    metrics = None
     for pl in plans:
-        eng.run_round(data, lab, offs, pl, args.opt, args.lr)
+        metrics = eng.run_round(data, lab, offs, pl, args.opt, args.lr)
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
-    ops.PROBE.reset()
-    ops.PROBE.tag, ops.PROBE.enabled = "*", True
-    eng.run_round(data, lab, offs, eng.make_plan(sizes, 1, generator=gen), args.opt, args.lr,
-                  serialize=True)
-    ops.PROBE.enabled = False
+    if dump and metrics is not None:  # the round's result: every client's trained row
+        dump_outputs(dump, round_outputs(None, None, metrics,
+                                         client_params=eng.params[:len(sizes), :eng.layout.P]))
     peak = FP32_MFMA_PEAK_TFLOPS
-    rows, instances, by_bucket, conv_all = summarize_instances(ops.PROBE.by_tag(),
-                                                               ops.PROBE.by_tag_bucket(), peak)
-    ridge = peak * 1e12 / (HBM_PEAK_GBS * 1e9)
-    ps = [(t, v) for t, v in rows if "psnorm" in t or "pswgrad" in t]
     value = sum(sizes) * steps / elapsed
     fl = TRAIN_FLOPS["simple_cnn"]
-    return {"metric": "client-images/sec/node", "value": round(value, 1),
+    head = {"metric": "client-images/sec/node", "value": round(value, 1),
             "unit": "client-images/s", "n_gpus": 1, "steps": steps, "warmup": warmup,
             "ms_per_step": round(1000 * elapsed / steps, 2), "higher_is_better": True,
             "scaling": "weak", "vs_baseline": None, "dtype": "f32",
@@ -829,13 +876,25 @@ def run_dpsgd(args, dev, steps, warmup):
                        "clients": len(sizes), "images_per_round": sum(sizes),
                        "lanes": eng.cut},
             "achieved_tflops_step": round(value * fl / 1e12, 2),
-            "round_frac": round(value * fl / 1e12 / peak, 4),
-            "roofline": roofline_of(rows[0][0], *rows[0][1], peak,
-                                    hbm=rows[0][1][2] <= ridge * rows[0][1][3]),
-            "roofline_psnorm": [roofline_of(t, *v, peak, hbm=v[2] <= ridge * v[3])
-                                for t, v in ps],
-            "conv_linear_all_launches": conv_all, "instances": instances,
-            "instances_by_clients": by_bucket, "_sizes": sizes}
+            "round_frac": round(value * fl / 1e12 / peak, 4), "_sizes": sizes}
+    if not args.full:
+        return head
+    ops.PROBE.reset()
+    ops.PROBE.tag, ops.PROBE.enabled = "*", True
+    eng.run_round(data, lab, offs, eng.make_plan(sizes, 1, generator=gen), args.opt, args.lr,
+                  serialize=True)
+    ops.PROBE.enabled = False
+    rows, instances, by_bucket, conv_all = summarize_instances(ops.PROBE.by_tag(),
+                                                               ops.PROBE.by_tag_bucket(), peak)
+    ridge = peak * 1e12 / (HBM_PEAK_GBS * 1e9)
+    ps = [(t, v) for t, v in rows if "psnorm" in t or "pswgrad" in t]
+    return dict(head,
+                roofline=roofline_of(rows[0][0], *rows[0][1], peak,
+                                     hbm=rows[0][1][2] <= ridge * rows[0][1][3]),
+                roofline_psnorm=[roofline_of(t, *v, peak, hbm=v[2] <= ridge * v[3])
+                                 for t, v in ps],
+                conv_linear_all_launches=conv_all, instances=instances,
+                instances_by_clients=by_bucket)
 
 
 def predict_strong(key, args, dev, worlds, steps, warmup):
@@ -1101,7 +1160,22 @@ def main():
     ap.add_argument("--separate-conv-bwd", action="store_true",
                     help="each layer's WGRAD and DGRAD as two launches (no dual-role launch): "
                          "the PMC traffic passes (tools/bench_traffic.py) attribute per kernel")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the instrumented per-launch-"
+                         "shape round and the roofline stretch, the K2 and K2-dpsgd blocks of "
+                         "the N=1 KT line, rounds-to-target, the CPU baselines and the detail "
+                         "file (the --no-* switches and --rounds-target 0 take parts out again)")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed rounds write what the last one computed (the new "
+                         "global model, or K2-dpsgd's client rows, and the clients' metrics) "
+                         "as DIR/<name>.npy; inputs and seeds are fixed, so two builds compare "
+                         "output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps: at least one timed round")
+    # the detail file belongs to --full; a plain run writes it only where the caller names one
+    if not args.full and args.detail_out == ap.get_default("detail_out"):
+        args.detail_out = ""
     if args.separate_conv_bwd:
         from fedhip import ops as _ops
         _ops.set_conv_pairing(False)
@@ -1116,19 +1190,20 @@ def main():
     if args.config == "K2-dpsgd":
         if world != 1:
             raise SystemExit("K2-dpsgd: one GPU only")
-        out = run_dpsgd(args, dev, args.steps, args.warmup)
-        if not args.no_cpu_baseline:
+        out = run_dpsgd(args, dev, args.steps, args.warmup, dump=args.dump_outputs)
+        if args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_dpsgd(out.pop("_sizes"), args.lr)
         out.pop("_sizes", None)
         out["env"] = {k: v for k, v in sorted(os.environ.items()) if k.startswith("FH_")}
         out["detail_file"] = write_detail(out, args.detail_out)
         print(json.dumps(compact(out)), flush=True)
         return
-    out = run_config(args.config, args, world, rank, dev, args.steps, args.warmup, rtt=True)
+    out = run_config(args.config, args, world, rank, dev, args.steps, args.warmup, rtt=True,
+                     dump=args.dump_outputs)
     # BASELINE.json's only 1-GPU config (K2: SimpleCNN, 32 Dirichlet(0.5) clients, update DP
-    # eps=1.0 timed) rides along the default N=1 line, measured the same way
+    # eps=1.0 timed) rides along the N=1 KT line of a --full run, measured the same way
     k2 = dps = None
-    if world == 1 and args.config == "KT" and not args.no_k2:
+    if args.full and world == 1 and args.config == "KT" and not args.no_k2:
         k2 = run_config("K2", args, world, rank, dev, max(args.steps, 3), args.warmup)
         # r06: north_star's per-sample clipping (K2-dpsgd) rides along too, so the driver
         # measures it: the same workload as `--config K2-dpsgd`

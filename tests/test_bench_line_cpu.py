@@ -132,6 +132,34 @@ def test_timed_passes_fixed_sample():
     assert n == 2 and imgs == 450  # median-first: 250 then 200
 
 
+def test_dump_outputs_files_and_budget(tmp_path, monkeypatch):
+    """--dump-outputs: one float32 / float64 .npy per output, whole when it fits; an array over
+    its share of the byte budget becomes the same seeded sample of its elements every time."""
+    import collections
+    import numpy as np
+    import torch
+    M = collections.namedtuple("M", "loss accuracy epochs_completed samples_processed")
+    flat = torch.arange(1000, dtype=torch.float32)
+    outs = bench.round_outputs(flat, None, [M(0.5, 0.25, 1, 64), M(1.5, 0.75, 1, 33)])
+    assert sorted(outs) == ["client_accuracy", "client_loss", "client_samples", "global_params"]
+    bench.dump_outputs(str(tmp_path / "a"), outs)
+    got = {f[:-4]: np.load(tmp_path / "a" / f) for f in sorted(os.listdir(tmp_path / "a"))}
+    assert sorted(got) == sorted(outs)
+    assert got["global_params"].dtype == np.float32
+    assert np.array_equal(got["global_params"], flat.numpy())
+    assert got["client_loss"].dtype == np.float64 and got["client_loss"].tolist() == [0.5, 1.5]
+    assert got["client_samples"].tolist() == [64.0, 33.0]
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", 4 * 400)  # 4 outputs: 100 floats each
+    bench.dump_outputs(str(tmp_path / "b"), outs)
+    bench.dump_outputs(str(tmp_path / "c"), outs)
+    b, c = (np.load(tmp_path / d / "global_params.npy") for d in "bc")
+    assert b.shape == (100,) and np.array_equal(b, c)
+    assert len(set(b.tolist())) == 100 and np.all(np.diff(b) > 0)  # distinct elements, in order
+    assert sum(os.path.getsize(tmp_path / "b" / f) - 128 for f in os.listdir(tmp_path / "b")) \
+        <= 4 * 400
+    assert np.load(tmp_path / "b" / "client_loss.npy").tolist() == [0.5, 1.5]  # small: whole
+
+
 def test_chain_assign_isolates_long_chain():
     """r06 partition.chain_assign (strong scaling): every client on exactly one rank, the
     modelled makespan never above LPT's, and on KT's fixed 32-client set at 8 ranks the rank

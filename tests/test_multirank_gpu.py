@@ -155,7 +155,7 @@ def test_bench_multirank_rehearsal():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
            "--steps", "1", "--warmup", "1", "--config", "K2", "--dist-backend", "gloo",
-           "--one-device", "--no-cpu-baseline", "--rounds-target", "0"]
+           "--one-device", "--full", "--no-cpu-baseline", "--rounds-target", "0"]
     r = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -196,11 +196,12 @@ def test_rankround_exact_mode_bitwise():
             assert np.array_equal(res[0][rnd + 1]["start"], r0["glob"])
 
 
-def test_bench_strong_scaling_rehearsal():
+def test_bench_strong_scaling_rehearsal(tmp_path):
     """bench.py --strong (r05): the config's fixed client set (K2: 32 clients) sharded (r06:
     partition.chain_assign) over
     2 ranks on cuda:0 over gloo, one all-reduce per round; the line says "strong" and counts
-    the same 32 clients as the one-GPU run."""
+    the same 32 clients as the one-GPU run.  A plain run (no --full): rank 0 writes the last
+    timed round's outputs where --dump-outputs says."""
     import json
     import subprocess
     import sys
@@ -210,11 +211,20 @@ def test_bench_strong_scaling_rehearsal():
            "--master-addr", "127.0.0.1", "--master-port", str(port), "bench.py", "--gpus", "2",
            "--steps", "1", "--warmup", "1", "--config", "K2", "--dist-backend", "gloo",
            "--one-device", "--no-cpu-baseline", "--rounds-target", "0", "--strong",
-           "--no-instances", "--detail-out", ""]
+           "--no-instances", "--detail-out", "", "--dump-outputs", str(tmp_path / "dump")]
     r = subprocess.run(cmd, cwd=repo, capture_output=True, text=True, timeout=400)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
     assert out["n_gpus"] == 2 and out["value"] > 0 and out["scaling"] == "strong"
+    assert out["steps"] == 1 and out["ms_per_step"] > 0 and out["roofline"] is None
     assert out["config"]["clients"] == 32
     import bench
+    glob_p = np.load(tmp_path / "dump" / "global_params.npy")
+    # the whole parameter vector (values unchecked: K2's eps=1 update noise, sigma ~4.8 per
+    # weight, leaves no finite model after the warm-up round) and rank 0's clients' metrics
+    model = bench.hm.ModelFactory.create_model("simple_cnn")
+    assert glob_p.dtype == np.float32
+    assert glob_p.shape == (sum(p.numel() for p in model.parameters()),)
+    seen = np.load(tmp_path / "dump" / "client_samples.npy")
+    assert seen.dtype == np.float64 and 0 < seen.sum() < out["config"]["images_per_round"]
     assert out["config"]["images_per_round"] == sum(bench.build_clients(bench.CONFIGS["K2"], 1)[1])

@@ -32,18 +32,18 @@ if [[ $ST == *s* ]]; then
   tail -1 $O/smoke.log
 fi
 if [[ $ST == *b* ]]; then
-  timeout -k 10 900 python bench.py --steps 20 --warmup 5 --detail-out $O/bench_detail.json > $O/bench.json 2> $O/bench.err
+  timeout -k 10 900 python bench.py --full --steps 20 --warmup 5 --detail-out $O/bench_detail.json > $O/bench.json 2> $O/bench.err
   summ $O/bench.json KT
 fi
 if [[ $ST == *k* ]]; then
   for C in K3 K4 K5 K2-dpsgd; do
-    timeout -k 10 500 python bench.py --config $C --rounds-target 0 --steps 3 --warmup 1 --detail-out $O/detail_$C.json > $O/bench_$C.json 2> $O/bench_$C.err
+    timeout -k 10 500 python bench.py --full --config $C --rounds-target 0 --steps 3 --warmup 1 --detail-out $O/detail_$C.json > $O/bench_$C.json 2> $O/bench_$C.err
     summ $O/bench_$C.json $C
   done
 fi
 if [[ $ST == *p* ]]; then
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --no-cpu-baseline --rounds-target 0 --detail-out $O/prof_detail.json > $O/prof_bench.json 2> $O/prof_bench.err
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o run -- python3 $R/bench.py --full --no-cpu-baseline --rounds-target 0 --detail-out $O/prof_detail.json > $O/prof_bench.json 2> $O/prof_bench.err
   python3 $R/tools/trace_summary.py $O/prof > $O/trace_summary.txt 2>&1 || true
   head -5 $O/trace_summary.txt
   python3 $R/tools/roofline_check.py $O/prof $O/prof_detail.json > $O/roofline_check.json 2>&1 || true
@@ -52,7 +52,7 @@ if [[ $ST == *p* ]]; then
 fi
 if [[ $ST == *q* ]]; then  # the same kernel trace with WGRAD / DGRAD as separate launches
   cd /tmp && export TMPDIR=/tmp
-  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sep -o run -- python3 $R/bench.py --no-cpu-baseline --rounds-target 0 --no-k2 --separate-conv-bwd --detail-out '' > $O/prof_sep_bench.json 2> $O/prof_sep_bench.err
+  timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_sep -o run -- python3 $R/bench.py --full --no-cpu-baseline --rounds-target 0 --no-k2 --separate-conv-bwd --detail-out '' > $O/prof_sep_bench.json 2> $O/prof_sep_bench.err
   python3 $R/tools/trace_summary.py $O/prof_sep > $O/trace_summary_sep.txt 2>&1 || true
   head -5 $O/trace_summary_sep.txt
   cd $R

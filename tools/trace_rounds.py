@@ -1,6 +1,6 @@
 """Per-round kernel time of a profiled bench run (rocprofv3 --kernel-trace CSV).
 
-The default bench issues, per config: warmup + timed rounds (lanes concurrent), then one
+The `--full` bench issues, per config: warmup + timed rounds (lanes concurrent), then one
 instrumented round whose launches are each preceded by a GPU spin (at::cuda::sleep).  The
 tracer serialises dispatches, so a kernel's duration here is its time alone on the chip.
 This prints, for the window before the first spin (warmup + timed rounds of the first
