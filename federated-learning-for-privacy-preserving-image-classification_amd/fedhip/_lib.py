@@ -187,6 +187,13 @@ SIGNATURES = {
     "fh_avgpool_fwd": (I32, [P, I64, P, I64, P, I32, I32, I32, I32, P]),
     "fh_avgpool_bwd": (I32, [P, I64, P, I64, P, I32, I32, I32, I32, P]),
     "fh_gather_batch": (I32, [P, P, P, I64, P, I64, P, I64, I64, P, I32, I32, P]),
+    "fh_dwconv3x3_fwd": (I32, [P, I64, P, I64, P, I64, P, I32, I32, I32, I32, I32, I32, I32, I32,
+                               I32, P]),
+    "fh_dwconv3x3_dgrad": (I32, [P, I64, P, I64, P, I64, P, I32, I32, I32, I32, I32, I32, I32,
+                                 I32, I32, I32, P]),
+    "fh_dwconv3x3_wgrad_workspace": (SZ, [I32, I32, I32, I32, I32, I32]),
+    "fh_dwconv3x3_wgrad": (I32, [P, I64, P, I64, P, I64, P, SZ, P, I32, I32, I32, I32, I32, I32,
+                                 I32, I32, I32, P]),
 }
 
 _lib = None

@@ -267,14 +267,15 @@ class PackedTrainer:
                   acc_seen=self.acc_seen, reset=reset)
         # (<= 16 classes: the head kernel stages W in LDS; CIFAR-100's 100-class head is
         # faster as separate launches, measured on K5)
-        if self.dpsgd is None and net.fused_head and self.batch <= 32 and net.num_classes <= 16:
+        if self.dpsgd is None and net.fused_head and self.batch <= 32 and \
+                net.num_classes <= 16 and net.head_fits:
             # the last linear layer, the loss and that layer's backward: one launch
             net.forward(self.params, self.bufs, n, counts, train=True, head=False)
             net.head_ce(self.params, self.grads, n, counts, **ce)
             self._backward_and_update(n, counts, first, adam_dev)
             return
         if self.dpsgd is not None and net.fused_head and self.batch <= 32 and \
-                net.num_classes <= 16:
+                net.num_classes <= 16 and net.head_fits:
             # the head without its weight gradient (clipped per image below)
             net.forward(self.params, self.bufs, n, counts, train=True, head=False)
             net.head_ce(self.params, self.grads, n, counts, wgrad=False, **ce)

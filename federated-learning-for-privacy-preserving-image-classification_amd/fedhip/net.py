@@ -1,7 +1,8 @@
 """Client-packed forward/backward programs for the reference CNN families.
 
-A ``PackedNet`` is built from a model instance (SimpleCNN, CIFAR10CNN or
-FederatedResNet — src/shared/models_pytorch.py:59-246 in the reference) and
+A ``PackedNet`` is built from a model instance (SimpleCNN, CIFAR10CNN,
+FederatedResNet or LightweightMobileNet — src/shared/models_pytorch.py:59-329 in the
+reference) and
 a capacity (client slots x batch).  It owns every activation / gradient
 buffer for the packed batch, preallocated once, laid out
 [slot][image][channel][h][w] (NCHW per client).  Parameters live in flat
@@ -95,10 +96,10 @@ class _Buf:
 
 def model_family(model):
     cls = type(model).__name__
-    if cls in ("SimpleCNN", "CIFAR10CNN", "FederatedResNet"):
+    if cls in ("SimpleCNN", "CIFAR10CNN", "FederatedResNet", "LightweightMobileNet"):
         return cls
     raise FedHipError(f"model {cls} is not on the HIP path (supported: SimpleCNN, CIFAR10CNN, "
-                      "FederatedResNet)")
+                      "FederatedResNet, LightweightMobileNet)")
 
 
 class PackedNet:
@@ -118,6 +119,11 @@ class PackedNet:
             self.blocks = self._resnet_blocks(model)
         elif self.family == "CIFAR10CNN":
             self.in_shape = (3, 32, 32)
+        elif self.family == "LightweightMobileNet":
+            self.in_shape = (model.conv1.in_channels, 32, 32)
+            self.stem_c = model.conv1.out_channels
+            self.blocks = self._mobilenet_blocks(model)
+            self.feat_c = model.classifier.in_features
         C = self.num_classes
         self.logits = self.A("logits", C)
         self.dlogits = self.A("dlogits", C)
@@ -229,6 +235,25 @@ class PackedNet:
                 h //= s
         return blocks
 
+    def _mobilenet_blocks(self, model):
+        blocks = []
+        h = 32
+        for i, blk in enumerate(model.features):
+            ci, co = blk.depthwise.in_channels, blk.pointwise.out_channels
+            s = blk.depthwise.stride[0]
+            blocks.append(dict(pfx=f"features.{i}", cin=ci, cout=co, stride=s, hin=h,
+                               hout=h // s))
+            h //= s
+        return blocks
+
+    @property
+    def head_fits(self):
+        """Whether the fused head launch (fh_linear_head_ce) takes this model's last layer on
+        its LDS-staged path: it stages x and W rows of at most 256 features, which every
+        family's head has except LightweightMobileNet at width > 0.5 (512 at width 1.0) —
+        that one runs the separate launches the > 16-class head runs."""
+        return self.family != "LightweightMobileNet" or self.feat_c <= 256
+
     def _seed(self, layer_id):
         """Philox key of a dropout site: seed * 1000003 + layer_id * 7919 (mod 2^64).  With
         seed_dev set (graph replay) the per-step part lives on the device and the kernel
@@ -255,6 +280,8 @@ class PackedNet:
             self._fwd_simple(params, n, counts, train)
         elif fam == "CIFAR10CNN":
             self._fwd_cifar(params, bufs, n, counts, train)
+        elif fam == "LightweightMobileNet":
+            self._fwd_mobilenet(params, bufs, n, counts, train)
         else:
             self._fwd_resnet(params, bufs, n, counts, train)
         return self.logits
@@ -276,6 +303,10 @@ class PackedNet:
             x, F, wname, dx = self._fc_in, 128, "fc2", A("dh1", 128)
             mask = A("m1", 128, dtype=torch.uint8) if self._fc_in is not A("h1", 128) else None
             relu = True
+        elif fam == "LightweightMobileNet":
+            F, wname = self.feat_c, "classifier"
+            x, dx = A("feat", F), A("dfeat", F)
+            mask, relu = None, False
         else:
             x, F, wname, dx = A("feat", 256), 256, "fc", A("dfeat", 256)
             mask, relu = None, False
@@ -294,6 +325,8 @@ class PackedNet:
             self._bwd_simple(params, grads, n, counts)
         elif fam == "CIFAR10CNN":
             self._bwd_cifar(params, grads, n, counts)
+        elif fam == "LightweightMobileNet":
+            self._bwd_mobilenet(params, grads, n, counts)
         else:
             self._bwd_resnet(params, grads, n, counts)
         self._head_done = False
@@ -925,6 +958,89 @@ class PackedNet:
         ops.conv2d_wgrad(self.x, dc0, W(G, "conv1.weight"), None, n, B, self.in_shape[0], 32, 32, 64,
                          3, 1, 1, counts=cnt)
 
+    # ---------------- LightweightMobileNet (models_pytorch.py:249-329)
+    def _fwd_mobilenet(self, P_, bufs, n, cnt, train):
+        """conv1 3x3 -> bn1 -> ReLU, six [depthwise 3x3(s) -> bn1 -> ReLU -> pointwise 1x1 ->
+        bn2 -> ReLU] blocks, global average pool, classifier.  Every BN output is
+        materialised (bn_fwd_train / bn_fwd_eval); the depthwise layers run on dwconv.hip,
+        the stem and the pointwise layers on the implicit-GEMM convolution."""
+        A, B, W = self.A, self.batch, self.W
+        c0 = self.stem_c
+        c, r = A("c_stem", c0, 32, 32), A("r_stem", c0, 32, 32)
+        ops.conv2d_fwd(self.x, W(P_, "conv1.weight"), None, c, n, B, self.in_shape[0], 32, 32, c0,
+                       3, 1, 1, counts=cnt)
+        self._bn_train(P_, bufs, "bn1", c, r, n, c0, 1024, cnt, relu=True, train=train)
+        xin = r
+        for b in self.blocks:
+            pf, ci, co, s, hi, ho = b["pfx"], b["cin"], b["cout"], b["stride"], b["hin"], b["hout"]
+            d, dr = A(f"{pf}.d", ci, ho, ho), A(f"{pf}.dr", ci, ho, ho)
+            ops.dwconv3x3_fwd(xin, W(P_, f"{pf}.depthwise.weight"), d, n, B, ci, hi, s, counts=cnt)
+            self._bn_train(P_, bufs, f"{pf}.bn1", d, dr, n, ci, ho * ho, cnt, relu=True,
+                           train=train)
+            p, pr = A(f"{pf}.p", co, ho, ho), A(f"{pf}.pr", co, ho, ho)
+            ops.conv2d_fwd(dr, W(P_, f"{pf}.pointwise.weight"), None, p, n, B, ci, ho, ho, co, 1, 1,
+                           0, counts=cnt)
+            self._bn_train(P_, bufs, f"{pf}.bn2", p, pr, n, co, ho * ho, cnt, relu=True,
+                           train=train)
+            xin = pr
+        f = A("feat", self.feat_c)
+        ho = self.blocks[-1]["hout"]
+        ops.avgpool_fwd(xin, f, n, B, self.feat_c, ho * ho, counts=cnt)
+        if self._head:
+            ops.linear_fwd(f, W(P_, "classifier.weight"), W(P_, "classifier.bias"), self.logits, n,
+                           B, self.feat_c, self.num_classes, counts=cnt)
+
+    def _bwd_mobilenet(self, P_, G, n, cnt):
+        A, B, W = self.A, self.batch, self.W
+        K, F = self.num_classes, self.feat_c
+        f, df = A("feat", F), A("dfeat", F)
+        if not self._head_done:
+            ops.linear_wgrad(f, self.dlogits, W(G, "classifier.weight"), W(G, "classifier.bias"),
+                             n, B, F, K, counts=cnt)
+            ops.linear_dgrad(self.dlogits, W(P_, "classifier.weight"), df, n, B, F, K, counts=cnt)
+        last = self.blocks[-1]
+        dout = A(f"{last['pfx']}.dpr", last["cout"], last["hout"], last["hout"])
+        ops.avgpool_bwd(df, dout, n, B, F, last["hout"] ** 2, counts=cnt)
+        for bi in range(len(self.blocks) - 1, -1, -1):
+            b = self.blocks[bi]
+            pf, ci, co, s, hi, ho = b["pfx"], b["cin"], b["cout"], b["stride"], b["hin"], b["hout"]
+            dpr = A(f"{pf}.dpr", co, ho, ho)
+            # bn2 (+ ReLU, its mask recomputed from the BN input) -> pointwise
+            dp = A(f"{pf}.dp", co, ho, ho)
+            sm2, si2 = self._bn_save(f"{pf}.bn2", co)
+            ops.bn_bwd(dpr, None, A(f"{pf}.p", co, ho, ho), W(P_, f"{pf}.bn2.weight"), sm2, si2, dp,
+                       W(G, f"{pf}.bn2.weight"), W(G, f"{pf}.bn2.bias"), n, B, co, ho * ho,
+                       relu=True, counts=cnt, beta=W(P_, f"{pf}.bn2.bias"))
+            ops.conv2d_wgrad(A(f"{pf}.dr", ci, ho, ho), dp, W(G, f"{pf}.pointwise.weight"), None, n,
+                             B, ci, ho, ho, co, 1, 1, 0, counts=cnt)
+            ddr = A(f"{pf}.ddr", ci, ho, ho)
+            ops.conv2d_dgrad(dp, W(P_, f"{pf}.pointwise.weight"), ddr, n, B, ci, ho, ho, co, 1, 1,
+                             0, counts=cnt)
+            # bn1 (+ ReLU) -> depthwise
+            dd = A(f"{pf}.dd", ci, ho, ho)
+            sm1, si1 = self._bn_save(f"{pf}.bn1", ci)
+            ops.bn_bwd(ddr, None, A(f"{pf}.d", ci, ho, ho), W(P_, f"{pf}.bn1.weight"), sm1, si1, dd,
+                       W(G, f"{pf}.bn1.weight"), W(G, f"{pf}.bn1.bias"), n, B, ci, ho * ho,
+                       relu=True, counts=cnt, beta=W(P_, f"{pf}.bn1.bias"))
+            # this block's input: the previous block's output (or the stem's), and its gradient
+            if bi > 0:
+                pb = self.blocks[bi - 1]
+                xin, din = A(f"{pb['pfx']}.pr", ci, hi, hi), A(f"{pb['pfx']}.dpr", ci, hi, hi)
+            else:
+                xin, din = A("r_stem", ci, hi, hi), A("dstem", ci, hi, hi)
+            ops.dwconv3x3_wgrad(xin, dd, W(G, f"{pf}.depthwise.weight"), n, B, ci, hi, s,
+                                counts=cnt)
+            ops.dwconv3x3_dgrad(dd, W(P_, f"{pf}.depthwise.weight"), din, n, B, ci, hi, s,
+                                counts=cnt)
+        c0 = self.stem_c
+        dc0 = A("dc_stem", c0, 32, 32)
+        sm, si = self._bn_save("bn1", c0)
+        ops.bn_bwd(A("dstem", c0, 32, 32), None, A("c_stem", c0, 32, 32), W(P_, "bn1.weight"), sm,
+                   si, dc0, W(G, "bn1.weight"), W(G, "bn1.bias"), n, B, c0, 1024, relu=True,
+                   counts=cnt, beta=W(P_, "bn1.bias"))
+        ops.conv2d_wgrad(self.x, dc0, W(G, "conv1.weight"), None, n, B, self.in_shape[0], 32, 32,
+                         c0, 3, 1, 1, counts=cnt)
+
     # -------------------------------------------------------------- decision buffers
     def pool_index_buffers(self):
         """(idx buffer, H, W) of every max-pool in forward order (uint8 window codes)."""
@@ -935,7 +1051,7 @@ class PackedNet:
         if self.family == "CIFAR10CNN":
             return [(A(f"i_{cv}", co, hw // 2, hw // 2, dtype=torch.uint8), hw, hw)
                     for i, (cv, ci, co, hw, bn) in enumerate(self._CIFAR_CONVS) if i % 2 == 1]
-        return []
+        return []  # FederatedResNet, LightweightMobileNet: no max-pool
 
     def relu_output_buffers(self):
         """Post-ReLU activations in forward order (their > 0 pattern is the ReLU mask)."""
@@ -970,6 +1086,12 @@ class PackedNet:
                 return out + [self._e1, self._e2]
             return [A(f"r_{cv}", co, hw, hw) for cv, ci, co, hw, bn in self._CIFAR_CONVS] + \
                 [self._e1, self._e2]
+        if self.family == "LightweightMobileNet":  # the stem and two maps per block: 13
+            out = [A("r_stem", self.stem_c, 32, 32)]
+            for b in self.blocks:
+                pf, ho = b["pfx"], b["hout"]
+                out += [A(f"{pf}.dr", b["cin"], ho, ho), A(f"{pf}.pr", b["cout"], ho, ho)]
+            return out
         out = [A("r_stem", 64, 32, 32)]
         for b in self.blocks:
             pf, co, ho = b["pfx"], b["cout"], b["hout"]

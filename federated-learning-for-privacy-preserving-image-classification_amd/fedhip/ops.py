@@ -1486,6 +1486,62 @@ def avgpool_bwd(dy, dx, nclients, batch, C, HW, counts=None):
          C, HW, stream_handle())
 
 
+# ------------------------------------------------------------------ depthwise 3x3 (dwconv.hip)
+def _dw_tag(kind, C, h, stride):
+    return f"dwconv_{kind}:c{C}x{h}x{h}k3s{stride}"
+
+
+def _dw_bytes(nclients, batch, C, h, stride):
+    """Algorithmic HBM bytes of one depthwise launch: the two activation tensors, each once."""
+    ho = h // stride
+    return 4.0 * nclients * batch * C * (h * h + ho * ho)
+
+
+def _dw_flops(nclients, batch, C, h, stride):
+    ho = h // stride
+    return 18.0 * nclients * batch * C * ho * ho
+
+
+def dwconv3x3_fwd(x, w, y, nclients, batch, C, h, stride, counts=None, k=3, pad=1):
+    """Depthwise (groups = C) 3x3/pad-1 convolution, stride 1 or 2, no bias
+    (fh_dwconv3x3_fwd): x [clients, batch, C, h, h] -> y [clients, batch, C, h/s, h/s];
+    w [clients, C * 9] may be any view into packed parameter rows."""
+    require_device(x, "x")
+    ev = PROBE.begin(_dw_tag("fwd", C, h, stride))
+    call("fh_dwconv3x3_fwd", ptr(x), _cs(x), ptr(w), _cs(w), ptr(y), _cs(y), _counts(counts),
+         nclients, batch, C, h, h, k, k, stride, pad, stream_handle())
+    PROBE.end(ev, _dw_flops(nclients, batch, C, h, stride),
+              _dw_bytes(nclients, batch, C, h, stride), nclients)
+    return y
+
+
+def dwconv3x3_dgrad(dy, w, dx, nclients, batch, C, h, stride, counts=None, accumulate=False, k=3,
+                    pad=1):
+    """Input gradient of dwconv3x3_fwd (fh_dwconv3x3_dgrad); h is the input map (dx).
+    accumulate: dx += result."""
+    require_device(dy, "dy")
+    ev = PROBE.begin(_dw_tag("dgrad", C, h, stride))
+    call("fh_dwconv3x3_dgrad", ptr(dy), _cs(dy), ptr(w), _cs(w), ptr(dx), _cs(dx),
+         _counts(counts), nclients, batch, C, h, h, k, k, stride, pad, int(accumulate),
+         stream_handle())
+    PROBE.end(ev, _dw_flops(nclients, batch, C, h, stride),
+              _dw_bytes(nclients, batch, C, h, stride), nclients)
+    return dx
+
+
+def dwconv3x3_wgrad(x, dy, dw, nclients, batch, C, h, stride, counts=None, k=3, pad=1):
+    """Weight gradient of dwconv3x3_fwd (fh_dwconv3x3_wgrad): dw [clients, C * 9] is
+    overwritten; a split sum's partials go through the workspace and are added in order."""
+    require_device(x, "x")
+    ws, nb = _ws_for("fh_dwconv3x3_wgrad_workspace", x.device, nclients, batch, C, h, h, stride)
+    ev = PROBE.begin(_dw_tag("wgrad", C, h, stride))
+    call("fh_dwconv3x3_wgrad", ptr(x), _cs(x), ptr(dy), _cs(dy), ptr(dw), _cs(dw), ptr(ws), nb,
+         _counts(counts), nclients, batch, C, h, h, k, k, stride, pad, stream_handle())
+    PROBE.end(ev, _dw_flops(nclients, batch, C, h, stride),
+              _dw_bytes(nclients, batch, C, h, stride), nclients)
+    return dw
+
+
 @dataclass(frozen=True)
 class DataTransform:
     """torchvision train/test transform of the reference loaders, run on the chip by

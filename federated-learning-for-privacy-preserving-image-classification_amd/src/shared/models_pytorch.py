@@ -138,8 +138,10 @@ class FederatedResNet(FederatedCNNBase):
 
 
 class LightweightMobileNet(FederatedCNNBase):
-    """Parameter container only: depthwise convolution is not on the HIP path
-    (no BASELINE config uses this model)."""
+    """Stem conv3x3-bn-relu, six [depthwise 3x3(s)-bn-relu, pointwise 1x1-bn-relu] blocks
+    (64,128,128,256,256,512 channels x width_multiplier; strides 1,2,1,2,1,2), global avgpool,
+    classifier.  On the HIP path for 32x32 inputs (depthwise layers: csrc/dwconv.hip); DP-SGD
+    is refused for it, as for every model with BatchNorm."""
 
     model_name = "lightweight_mobilenet"
 

@@ -865,6 +865,33 @@ int fh_avgpool_bwd(const float* dy, int64_t dy_cs, float* dx, int64_t dx_cs,
                    const int32_t* counts, int32_t nclients, int32_t batch, int32_t C, int32_t HW,
                    void* stream);
 
+/* ---------------- depthwise 3x3 convolution (groups = channels) ------------
+ * LightweightMobileNet's depthwise layers (models_pytorch.py DepthwiseSeparableConv): no bias,
+ * x: [clients][batch][C][h][w]; w: [C][1][3][3] per client (any 4-byte aligned offset of a
+ * packed parameter row); y: [clients][batch][C][h/stride][w/stride].  Supported: 3x3, pad 1,
+ * stride 1 or 2, square maps of 8, 16 or 32, C % 8 == 0, activations 16-byte aligned with
+ * client strides % 4 == 0; anything else returns FH_E_UNSUPPORTED.  Images >= counts[client]
+ * are neither read nor written.  Deterministic (no atomics); plain fp32 multiply-adds. */
+int fh_dwconv3x3_fwd(const float* x, int64_t x_cs, const float* w, int64_t w_cs, float* y,
+                     int64_t y_cs, const int32_t* counts, int32_t nclients, int32_t batch,
+                     int32_t C, int32_t h, int32_t w_, int32_t kh, int32_t kw, int32_t stride,
+                     int32_t pad, void* stream);
+/* h / w_: the INPUT map (dx); dy is [C][h/stride][w_/stride].  accumulate = 1: dx += result. */
+int fh_dwconv3x3_dgrad(const float* dy, int64_t dy_cs, const float* w, int64_t w_cs, float* dx,
+                       int64_t dx_cs, const int32_t* counts, int32_t nclients, int32_t batch,
+                       int32_t C, int32_t h, int32_t w_, int32_t kh, int32_t kw, int32_t stride,
+                       int32_t pad, int32_t accumulate, void* stream);
+/* dw is overwritten.  With few (client, channel) pairs the sum is split over image ranges
+ * through `workspace` (>= fh_dwconv3x3_wgrad_workspace(...) bytes; 0 = never splits; a NULL /
+ * too-small workspace disables the split) and the partials are added in split order by a
+ * second launch. */
+size_t fh_dwconv3x3_wgrad_workspace(int32_t nclients, int32_t batch, int32_t C, int32_t h,
+                                    int32_t w_, int32_t stride);
+int fh_dwconv3x3_wgrad(const float* x, int64_t x_cs, const float* dy, int64_t dy_cs, float* dw,
+                       int64_t dw_cs, void* workspace, size_t ws_bytes, const int32_t* counts,
+                       int32_t nclients, int32_t batch, int32_t C, int32_t h, int32_t w_,
+                       int32_t kh, int32_t kw, int32_t stride, int32_t pad, void* stream);
+
 /* ---------------- on-device batch assembly (DataLoader replacement) -------
  * x[z][b] = data[idx[z*idx_cs+b]], y[z][b] = labels[idx[..]] for b < counts[z]. */
 int fh_gather_batch(const float* data, const int64_t* labels, const int64_t* idx, int64_t idx_cs,
