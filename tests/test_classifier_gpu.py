@@ -87,6 +87,18 @@ def test_head_matches_separate_ops(nc, F, K, p):
             e_new = (got.double() - ref).abs().max().item() / scale
             e_old = (sep.double() - ref).abs().max().item() / scale
             assert e_new <= max(4 * e_old, 2e-6), (e_new, e_old)
+        # the baseline's own dlogits, measured directly: fh_ce_fwd_bwd on the logits it was
+        # given against fp64 on those logits, with torch's fp32 CPU cross-entropy (+ autograd)
+        # as the yardstick — a wrong dl1 would otherwise only raise e_old above
+        lg_c = lg1[z, :n].cpu()
+        x32 = lg_c.clone().requires_grad_(True)
+        torch.nn.functional.cross_entropy(x32, tgt.cpu()).backward()
+        dl64 = (torch.log_softmax(lg_c.double(), dim=1).exp() -
+                torch.nn.functional.one_hot(tgt.cpu(), K).double()) / n
+        scale = dl64.abs().max().item() + 1e-12
+        e_ce = (dl1[z, :n].cpu().double() - dl64).abs().max().item() / scale
+        e_cpu = (x32.grad.double() - dl64).abs().max().item() / scale
+        assert e_ce <= max(4 * e_cpu, 2e-6), (e_ce, e_cpu)
         assert abs(loss2[z].item() - loss_t.item()) <= 2e-6 * max(1.0, abs(loss_t.item()))
         assert abs(loss2[z].item() - loss1[z].item()) <= 2e-6 * max(1.0, abs(loss1[z].item()))
     # accumulators: same increments (loss sums as float64 of the fp32 batch losses)

@@ -412,3 +412,72 @@ def test_dpsgd_deferred_dgrad_reduction_bit_identical(sizes):
     assert taken[0][0] >= 2 and taken[0][1] >= 2 and taken[1] == (0, 0), taken
     assert torch.equal(engs[0].params, engs[1].params)
     assert torch.equal(engs[0].state1, engs[1].state1)
+
+
+@pytest.mark.parametrize("cin,cout,h,k,stride,pad", [
+    (32, 64, 8, 3, 1, 1),    # the smallest map of the direct per-image kernel: cross-checked
+    (32, 64, 8, 3, 2, 1),    # 16 output pixels: less than one 32-pixel K step
+    (16, 24, 7, 1, 1, 0),    # partial tiles in both dimensions, odd map
+    (20, 130, 6, 3, 1, 1),   # two tiles of output channels, two of cin * 9
+    (8, 40, 8, 1, 2, 0)])
+@pytest.mark.parametrize("with_bias", [True, False])
+def test_persample_conv_sqnorm_exact(cin, cout, h, k, stride, pad, with_bias):
+    """fh_conv2d_persample_sqnorm (implicit-GEMM WGRAD, one split per image, each tile reduced
+    to a sum of squares): sqnorm[z][i] += ||dW_i||^2 (+ ||db_i||^2) — equal to the fp64 norm
+    of the autograd per-image gradient on operands in {-1, 0, 1}.  Every per-image total is
+    below 2^24, so every fp32 partial sum of squares is an exact integer whatever the order.
+    Accumulates over calls; entries past a client's count receive +0."""
+    import torch.nn.functional as F
+    nc, B = 3, 5
+    counts = [5, 1, 3]
+    oh = (h + 2 * pad - k) // stride + 1
+    g = torch.Generator().manual_seed(40 + cin + cout + stride)
+    x = torch.randint(-1, 2, (nc, B, cin, h, h), generator=g).float()
+    dy = torch.randint(-1, 2, (nc, B, cout, oh, oh), generator=g).float()
+    want = torch.zeros(nc, B, dtype=torch.float64)
+    for z in range(nc):
+        for i in range(counts[z]):
+            w = torch.zeros(cout, cin, k, k, dtype=torch.float64, requires_grad=True)
+            b = torch.zeros(cout, dtype=torch.float64, requires_grad=True)
+            F.conv2d(x[z, i:i + 1].double(), w, b, stride=stride, padding=pad).backward(
+                dy[z, i:i + 1].double())
+            want[z, i] = (w.grad ** 2).sum() + ((b.grad ** 2).sum() if with_bias else 0.0)
+    assert float(want.max()) < 2.0 ** 24 and all(float(want[z, 0]) > 0 for z in range(nc))
+    # images past a client's count hold NaN: nothing valid may depend on them
+    xd, dyd = x.to(DEV), dy.to(DEV)
+    for z in range(nc):
+        xd[z, counts[z]:] = float("nan")
+        dyd[z, counts[z]:] = float("nan")
+    cd = torch.tensor(counts, dtype=torch.int32, device=DEV)
+    base = torch.arange(nc * B, dtype=torch.float64).view(nc, B) * 0.5 - 3.0
+    sq = base.to(DEV)
+    ops.conv2d_persample_sqnorm(xd, dyd, sq, nc, B, cin, h, h, cout, k, stride, pad,
+                                with_bias=with_bias, counts=cd)
+    torch.cuda.synchronize()
+    assert torch.equal(sq.cpu(), base + want)       # += ; +0 past the counts
+    ops.conv2d_persample_sqnorm(xd, dyd, sq, nc, B, cin, h, h, cout, k, stride, pad,
+                                with_bias=with_bias, counts=cd)
+    torch.cuda.synchronize()
+    assert torch.equal(sq.cpu(), base + want + want)
+    if (k, stride, h) == (3, 1, 8) and with_bias:
+        # the per-image slabs of the direct kernel, on the same inputs
+        slab = ops.PersampleSlab(DEV)
+        xz, dyz = torch.nan_to_num(xd), torch.nan_to_num(dyd)
+        ops.conv2d_wgrad_persample(xz, dyz, slab, nc, B, cin, h, h, cout, counts=cd)
+        sq2 = torch.zeros(nc, B, dtype=torch.float64, device=DEV)
+        ops.slab_sqnorm(slab, sq2, counts=cd)
+        torch.cuda.synchronize()
+        assert torch.equal(sq2.cpu(), want)
+
+
+def test_persample_conv_sqnorm_refuses_unsupported_kernels():
+    """A kernel size the implicit GEMM has no instantiation for is a host-side error: no
+    launch, sqnorm untouched."""
+    nc, B, cin, cout, h = 1, 2, 8, 8, 8
+    x = torch.ones(nc, B, cin, h, h, device=DEV)
+    dy = torch.ones(nc, B, cout, h, h, device=DEV)
+    sq = torch.full((nc, B), 7.0, dtype=torch.float64, device=DEV)
+    with pytest.raises(FedHipError, match="unsupported kernel 5x5 stride 1"):
+        ops.conv2d_persample_sqnorm(x, dy, sq, nc, B, cin, h, h, cout, 5, 1, 2)
+    torch.cuda.synchronize()
+    assert torch.equal(sq.cpu(), torch.full((nc, B), 7.0, dtype=torch.float64))
