@@ -133,7 +133,9 @@ def _ulps(a, b):
 @pytest.mark.parametrize("nc,ci,co,hw,affine", [(1, 32, 32, 32, True), (1, 3, 32, 32, False),
                                                 (1, 64, 128, 8, True), (3, 32, 64, 16, True),
                                                 (32, 32, 32, 32, True), (32, 64, 64, 16, False),
-                                                (24, 128, 128, 8, True), (9, 64, 128, 8, False)])
+                                                (24, 128, 128, 8, True), (9, 64, 128, 8, False),
+                                                (1, 32, 64, 16, True), (2, 64, 64, 16, True),
+                                                (1, 128, 128, 8, True)])
 def test_epilogue_bn_stats_match_separate_pass(nc, ci, co, hw, affine):
     """fh_conv2d_fwd_bnstats + fh_bn_finalize_tiles vs fh_conv2d_fwd_bnrelu + fh_bn_fwd_stats:
     y bit-identical; the per-tile fp64 partials equal fp64 sums of the stored y; the BN
@@ -349,7 +351,7 @@ def test_dgrad_bn_bwd_epilogue_rounds_match(opt):
 
 @pytest.mark.parametrize("nc,ci,co,hw,dm", [(1, 32, 64, 16, True), (32, 32, 64, 16, True),
                                             (3, 64, 128, 8, False), (1, 64, 128, 8, True),
-                                            (24, 64, 128, 8, True)])
+                                            (24, 64, 128, 8, True), (1, 64, 64, 16, True)])
 def test_dgrad_bn_bwd_stats_through_pool(nc, ci, co, hw, dm):
     """fh_conv2d_dgrad_bnstats with pidx (the BN-ReLU output went through a 2x2 max-pool and
     dropout) + fh_bn_bwd_pool_tiles vs fh_conv2d_dgrad + fh_bn_bwd_pool: dX bit-identical,

@@ -15,9 +15,9 @@ pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
 
 
-@pytest.mark.parametrize("nc", [1, 3, 9, 20])
+@pytest.mark.parametrize("nc", [1, 2, 3, 9, 20])
 def test_conv_relu_pool_op_matches_separate_launches(nc):
-    """nc = 1 / 3: the planner splits over input channels (pool in the split reduction);
+    """nc = 1 / 2 / 3: the planner splits over input channels (pool in the split reduction);
     9 / 20: unsplit BM = 32 / 64 launches (pool in the conv's epilogue)."""
     B, H, cin, cout = 32, 16, 32, 64
     torch.manual_seed(nc)
