@@ -1709,12 +1709,12 @@ thread_local DgradDefer g_ddef;
 // summed while staging (the rest were materialised by the skipped epilogue launch)
 thread_local int64_t g_ddef_deferred = 0, g_ddef_taken = 0;
 
-// Split reduction left to the BatchNorm call after the conv (fh_conv_bn_defer, r06,
-// splitbn.h): armed by the host for the next fh_conv2d_{fwd,dgrad}_bnstats call, recorded by
+// Split FWD reduction left to the BatchNorm finalize after the conv (fh_conv_bn_defer, r06,
+// splitbn.h): armed by the host for the next fh_conv2d_fwd_bnstats call, recorded by
 // run_dconv in place of its splitk_epilogue_kernel launch, consumed by the BN call (bn.hip);
 // anything else that finds it pending launches the skipped epilogue (sbn_materialize).
 thread_local SplitBnRec g_sbn;
-thread_local int g_sbn_armed = 0;  // fh_conv_bn_defer(max) -> the next _bnstats call
+thread_local int g_sbn_armed = 0;  // fh_conv_bn_defer(max) -> the next fwd_bnstats call
 thread_local int g_sbn_want = 0;   // ... inside that call
 thread_local int64_t g_sbn_deferred = 0;
 
@@ -1727,10 +1727,7 @@ int sbn_materialize() {
     dim3 eg((unsigned)ceil_div(r.Nfull, 256), (unsigned)r.M, (unsigned)r.nclients);
     FH_LAUNCH(splitk_epilogue_kernel, eg, dim3(256), 0, r.st, r.part, r.splits, r.M, (int)r.Nfull,
               r.out, r.out_cs, r.bias, r.b_cs, 0, 0, r.counts, r.batch, r.sp, r.bn_part,
-              r.bn_tiles, DropArgs{},
-              BnBwdEpi{r.bnx, r.bnx_cs, r.bn_scale, r.bn_shift, r.bns_cs, r.bn_mean, r.pidx,
-                       r.pmask, r.pi_cs, r.pm_cs, r.pscale, r.pw},
-              PoolEpi{});
+              r.bn_tiles, DropArgs{}, BnBwdEpi{}, PoolEpi{});
     FH_LAUNCH_CHECK("split conv reduction (deferred)");
     return FH_OK;
 }
@@ -1921,27 +1918,20 @@ static int run_dconv(DConvArgs a, int w, int nclients, void* ws, size_t ws_bytes
         }
     }
     if (p.splits > 1) {
-        if (sbn_want && S == 1 && a.bn_part && !a.accumulate && !a.relu && !a.pool_y &&
-            p.splits <= 4 && (int64_t)a.batch * sp <= std::min(sbn_want, kSbnMaxElems) &&
-            a.bn_tiles == ceil_div(a.Nfull, 256) &&
-            (OP == OP_FWD ? a.bnx == nullptr : a.bnx != nullptr)) {
+        if (sbn_want && OP == OP_FWD && S == 1 && a.bn_part && !a.accumulate && !a.relu &&
+            !a.pool_y && p.splits <= 4 &&
+            (int64_t)a.batch * sp <= std::min(sbn_want, kSbnMaxElems) &&
+            a.bn_tiles == ceil_div(a.Nfull, 256) && a.bnx == nullptr) {
             // the BN call after this conv sums the slab (splitbn.h, fh_conv_bn_defer)
             SplitBnRec& r = g_sbn;
             r = SplitBnRec{};
-            r.op = OP == OP_FWD ? 0 : 1;
             r.part = (const float*)ws;
             r.splits = p.splits; r.M = a.M; r.sp = sp; r.batch = a.batch; r.nclients = nclients;
             r.Nfull = a.Nfull;
             r.out = out; r.out_cs = a.out_cs;
-            r.bias = OP == OP_FWD ? a.bias : nullptr; r.b_cs = a.b_cs;
+            r.bias = a.bias; r.b_cs = a.b_cs;
             r.counts = a.counts;
             r.bn_part = a.bn_part; r.bn_tiles = a.bn_tiles;
-            if (OP != OP_FWD) {
-                r.bnx = a.bnx; r.bnx_cs = a.bnx_cs; r.bn_scale = a.bn_scale;
-                r.bn_shift = a.bn_shift; r.bns_cs = a.bns_cs; r.bn_mean = a.bn_mean;
-                r.pidx = a.pidx; r.pmask = a.pmask; r.pi_cs = a.pi_cs; r.pm_cs = a.pm_cs;
-                r.pscale = a.pscale; r.pw = w;
-            }
             r.st = st;
             r.pending = true;
             ++g_sbn_deferred;
@@ -2196,13 +2186,11 @@ extern "C" int fh_conv_defer_dgrad(int32_t on) {
     return FH_OK;
 }
 
-// fh_conv_bn_defer(1): the calling thread's next fh_conv2d_fwd_bnstats /
-// fh_conv2d_dgrad_bnstats call, when it plans a split direct launch, leaves its split reduction
-// to the BatchNorm call that consumes its statistics (fh_bn_finalize_tiles,
-// fh_maxpool2_fwd_bnfinalize, fh_bn_bwd_tiles, fh_bn_bwd_pool_tiles), which then sums the slab
-// and runs the BN pass as one launch — bit-identical outputs (splitbn.h).  A DGRAD's stored
-// gradient (dX) is then never written: only that BN call reads it.  Any other library call
-// that finds the reduction pending launches it first.  max_elems: the largest batch x plane
+// fh_conv_bn_defer(1): the calling thread's next fh_conv2d_fwd_bnstats call, when it plans a
+// split direct launch, leaves its split reduction to the BatchNorm call that consumes its
+// statistics (fh_bn_finalize_tiles, fh_maxpool2_fwd_bnfinalize), which then sums the slab and
+// runs the BN pass as one launch — bit-identical outputs (splitbn.h).  Another direct-conv or
+// fh_bn_* call that finds the reduction pending launches it first.  max_elems: the largest batch x plane
 // (elements per client and channel, <= 8192) the fusion takes; 0 disarms.
 extern "C" int fh_conv_bn_defer(int32_t max_elems) {
     FH_REQUIRE(max_elems >= 0, "conv_bn_defer: %d", max_elems);
@@ -2549,12 +2537,9 @@ extern "C" int fh_conv2d_dgrad_bnstats(const float* dy, int64_t dy_cs, const flo
     FH_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "conv2d_dgrad_bnstats: p=%g", p_drop);
     d.pidx = pidx; d.pmask = pidx ? pmask : nullptr; d.pi_cs = pi_cs; d.pm_cs = pm_cs;
     d.pscale = 1.0f / (1.0f - p_drop);
-    g_sbn_want = g_sbn_armed;
-    g_sbn_armed = 0;
-    rc = run_dconv<OP_DGRAD>(d, w_, nclients, workspace, ws_bytes, h * w_, as_stream(stream),
-                             "conv2d_dgrad_bnstats");
-    g_sbn_want = 0;
-    return rc;
+    g_sbn_armed = 0;  // an arm (fh_conv_bn_defer) is spent by the next _bnstats call, this one too
+    return run_dconv<OP_DGRAD>(d, w_, nclients, workspace, ws_bytes, h * w_, as_stream(stream),
+                               "conv2d_dgrad_bnstats");
 }
 
 // The DGRAD of a ResNet down-sampling block's input in one launch (models_pytorch.py:176-194:

@@ -761,7 +761,6 @@ class PackedNet:
                           self._bn_save(pbn, ci)[0], bn_tiles,
                           A(f"i_{pcv}", ci, hw, hw, dtype=torch.uint8),
                           A(f"m_{pcv}", ci, hw, hw, dtype=torch.uint8) if dm else None, p)
-                    ops.conv_bn_defer()  # a split plan's reduction joins bn_bwd_pool_tiles
                 ops.conv2d_dgrad(dc, W(P_, f"{cv}.weight"), dq, n, B, ci, hw, hw, co, 3, 1, 1,
                                  counts=cnt, bn_bwd=bb)
             else:
@@ -771,7 +770,6 @@ class PackedNet:
                     bn_tiles = self._bn_part(f"{pbn}.bwd", ci, hw)
                     bb = (A(f"c_{pcv}", ci, hw, hw), *self._bn_affine(pbn, ci),
                           self._bn_save(pbn, ci)[0], bn_tiles)
-                    ops.conv_bn_defer()  # ... joins bn_bwd_tiles
                 ops.conv2d_dgrad(dc, W(P_, f"{cv}.weight"), A(f"dr_{pcv}", ci, hw, hw), n, B, ci,
                                  hw, hw, co, 3, 1, 1, counts=cnt, bn_bwd=bb)
             ops.conv_pair(0)
@@ -907,7 +905,6 @@ class PackedNet:
             if self._fused and self.bn_bwd_epilogue:
                 # conv2's dgrad masks by bn1's ReLU and leaves bn1's backward statistics
                 tiles = self._bn_part(f"{pf}.bn1.bwd", co, ho)
-                ops.conv_bn_defer()  # ... and bn1's backward apply
                 ops.conv2d_dgrad(db, W(P_, f"{pf}.conv2.weight"), dar, n, B, co, ho, ho, co, 3, 1,
                                  1, counts=cnt, bn_bwd=(a, *aff1, sm1, tiles))
                 ops.conv_pair(0)

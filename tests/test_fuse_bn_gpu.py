@@ -2,7 +2,8 @@
 fh_conv2d_wgrad_bnrelu, fh_maxpool2_fwd_bnrelu) is bit-identical to the materialised path
 (fh_bn_fwd_train's apply pass + plain conv / pool): the consumer evaluates the same fp32
 operations on load.  Whole CIFAR10CNN rounds (graph replay, dropout, ragged batches) and
-the single ops on ragged client counts."""
+the single ops on ragged client counts; whole rounds on split plans (one or a few clients),
+eager against graph replay."""
 import pytest
 import torch
 
@@ -135,7 +136,8 @@ def _ulps(a, b):
                                                 (32, 32, 32, 32, True), (32, 64, 64, 16, False),
                                                 (24, 128, 128, 8, True), (9, 64, 128, 8, False),
                                                 (1, 32, 64, 16, True), (2, 64, 64, 16, True),
-                                                (1, 128, 128, 8, True)])
+                                                (1, 128, 128, 8, True), (1, 64, 64, 16, True),
+                                                (2, 64, 128, 8, True)])
 def test_epilogue_bn_stats_match_separate_pass(nc, ci, co, hw, affine):
     """fh_conv2d_fwd_bnstats + fh_bn_finalize_tiles vs fh_conv2d_fwd_bnrelu + fh_bn_fwd_stats:
     y bit-identical; the per-tile fp64 partials equal fp64 sums of the stored y; the BN
@@ -216,7 +218,8 @@ def test_fused_entry_points_refuse_unsupported_shapes():
 
 
 @pytest.mark.parametrize("nc,C,hw,dm", [(1, 32, 32, 1), (5, 64, 16, 1), (3, 128, 8, 0),
-                                        (24, 32, 32, 1)])
+                                        (24, 32, 32, 1), (1, 64, 16, 1), (1, 128, 8, 1),
+                                        (2, 128, 8, 0)])
 def test_pool_finalize_matches_separate_launches(nc, C, hw, dm):
     """fh_maxpool2_fwd_bnfinalize == fh_bn_finalize_tiles + fh_maxpool2_fwd_bnrelu: the BN
     outputs within 1 ulp (tree vs sequential merge of the same fp64 partials); the pooled
@@ -272,7 +275,7 @@ def test_pool_finalize_matches_separate_launches(nc, C, hw, dm):
 # unsplit (many clients) and split-K (one client) DGRAD epilogues, every map width, ragged
 @pytest.mark.parametrize("nc,ci,co,hw", [(1, 32, 32, 32), (32, 32, 32, 32), (3, 64, 64, 16),
                                          (1, 64, 64, 16), (24, 128, 128, 8), (1, 128, 128, 8),
-                                         (5, 32, 64, 16)])
+                                         (5, 32, 64, 16), (1, 64, 128, 8), (3, 64, 128, 8)])
 def test_dgrad_bn_bwd_stats_match_separate_pass(nc, ci, co, hw):
     """fh_conv2d_dgrad_bnstats + fh_bn_bwd_tiles vs fh_conv2d_dgrad + fh_bn_bwd (relu, mask
     recomputed from x): the stored g is dX with the ReLU mask applied, bit for bit; the
@@ -351,7 +354,8 @@ def test_dgrad_bn_bwd_epilogue_rounds_match(opt):
 
 @pytest.mark.parametrize("nc,ci,co,hw,dm", [(1, 32, 64, 16, True), (32, 32, 64, 16, True),
                                             (3, 64, 128, 8, False), (1, 64, 128, 8, True),
-                                            (24, 64, 128, 8, True), (1, 64, 64, 16, True)])
+                                            (24, 64, 128, 8, True), (1, 64, 64, 16, True),
+                                            (2, 32, 64, 16, False)])
 def test_dgrad_bn_bwd_stats_through_pool(nc, ci, co, hw, dm):
     """fh_conv2d_dgrad_bnstats with pidx (the BN-ReLU output went through a 2x2 max-pool and
     dropout) + fh_bn_bwd_pool_tiles vs fh_conv2d_dgrad + fh_bn_bwd_pool: dX bit-identical,
@@ -499,3 +503,34 @@ def test_bn_apply_tiles_matches_fwd_train(nc, C, hw, res):
     y = outs[1][0]
     for z in range(nc):
         assert bool((y[z, int(cnt[z]):] == 7.0).all())
+
+
+def _rounds(model_name, sizes, graphs, **kw):
+    torch.manual_seed(0)
+    model = hm.ModelFactory.create_model(model_name, **kw).to(DEV)
+    eng = PackedTrainer(model, capacity=len(sizes), batch=32, device=DEV)
+    eng.use_graphs = graphs
+    for k in range(len(sizes)):
+        eng.load_module_state(k, model)
+    g = torch.Generator().manual_seed(5)
+    data = torch.randn(sum(sizes), 3, 32, 32, generator=g).to(DEV)
+    labels = torch.randint(0, 10, (sum(sizes),), generator=g).to(DEV)
+    offs = [sum(sizes[:k]) for k in range(len(sizes))]
+    gen = torch.Generator().manual_seed(11)
+    for r in range(2):
+        plan = eng.make_plan(sizes, 1, generator=gen)
+        eng.run_round(data, labels, offs, plan, "sgd", 1e-2, seed=r)
+    torch.cuda.synchronize()
+    return eng.params[:len(sizes)].clone(), eng.bufs[:len(sizes)].clone()
+
+
+@pytest.mark.parametrize("model_name,kw", [("cifar10_cnn", {"dropout_rate": 0.3}),
+                                           ("federated_resnet", {"num_blocks": [1, 1, 1]})],
+                         ids=["cifar10_cnn", "federated_resnet"])
+def test_split_plan_rounds_eager_equals_replayed(model_name, kw):
+    """One-client and ragged steps (split plans): the trained rows and BN buffers after eager
+    rounds equal those after graph-replayed rounds bit for bit."""
+    sizes = [100, 37, 9]
+    p_e, b_e = _rounds(model_name, sizes, False, **kw)
+    p_g, b_g = _rounds(model_name, sizes, True, **kw)
+    assert torch.equal(p_e, p_g) and torch.equal(b_e, b_g)

@@ -1,11 +1,12 @@
-"""r06: a split direct conv's reduction inside the BatchNorm call after it (fh_conv_bn_defer,
-splitbn.h): one launch per (channel, client) instead of splitk_epilogue_kernel + bn_finalize /
-maxpool2_bnfin / bn_bwd_apply.  Against the same calls unarmed (the two launches): every
-stored tensor bit for bit — the convolution output, the BN affine, saved and running
-statistics, the pooled output / argmax / keep-mask, dgamma / dbeta and dx — on split plans
-(one or a few clients, ragged counts, with and without dropout); the launches really fused
-(fh_conv_bn_defer_status); whole CIFAR10CNN and ResNet rounds bit-identical with the fusion
-on and off, eager and replayed.
+"""r06: a split direct FWD conv's reduction inside the BatchNorm call after it
+(fh_conv_bn_defer, splitbn.h): one launch per (channel, client) instead of
+splitk_epilogue_kernel + bn_finalize / maxpool2_bnfin.  Against the same calls unarmed (the two
+launches): every stored tensor bit for bit — the convolution output, the BN affine, saved and
+running statistics, the pooled output / argmax / keep-mask — on split plans (one or a few
+clients, ragged counts, with and without dropout); the launches really fused
+(fh_conv_bn_defer_status); whole CIFAR10CNN rounds bit-identical with the fusion on and off,
+eager and replayed (with one block per stage no ResNet FWD conv takes the fusion; its rounds are
+test_fuse_bn_gpu.py's test_split_plan_rounds_eager_equals_replayed).
 Reference: BatchNorm2d after Conv2d, src/shared/models_pytorch.py:133-150, 189-194."""
 import pytest
 import torch
@@ -108,57 +109,6 @@ def test_fwd_reduction_in_finalize_bitwise(nc, ci, co, hw, pool, dm):
         _eq(a, c, cnt)
 
 
-@pytest.mark.parametrize("nc,ci,co,hw,pooled,dm", [
-    (1, 64, 64, 16, False, False), (1, 64, 128, 8, False, False), (1, 32, 64, 16, True, True),
-    (1, 64, 128, 8, True, True), (2, 32, 64, 16, True, False), (3, 64, 128, 8, False, False)])
-def test_dgrad_reduction_in_bn_backward_bitwise(nc, ci, co, hw, pooled, dm):
-    """CIFAR10CNN conv k+1's DGRAD -> BN k's backward: unpooled (bn_bwd_tiles) and through the
-    2x2 max-pool + dropout (bn_bwd_pool_tiles)."""
-    torch.manual_seed(nc * 11 + ci + hw + pooled)
-    cnt = _counts(nc, co + hw)
-    H = 2 * hw if pooled else hw
-    p = 0.3 if dm else 0.0
-    bx = torch.randn(nc, B, ci, H, H, device=DEV) * 1.3 + 0.1
-    gamma = torch.rand(nc, ci, device=DEV) + 0.5
-    gamma[:, ::5] *= -1
-    beta = torch.randn(nc, ci, device=DEV) * 0.3
-    rm, rv = torch.zeros(nc, ci, device=DEV), torch.ones(nc, ci, device=DEV)
-    sm, si = torch.zeros(nc, ci, device=DEV), torch.zeros(nc, ci, device=DEV)
-    sc, sh = torch.zeros(nc, ci, device=DEV), torch.zeros(nc, ci, device=DEV)
-    ops.bn_fwd_stats(bx, gamma, beta, rm, rv, sm, si, sc, sh, nc, B, ci, H * H, counts=cnt)
-    idx = msk = None
-    if pooled:
-        q = torch.zeros(nc, B, ci, hw, hw, device=DEV)
-        idx = torch.zeros(nc, B, ci, hw, hw, dtype=torch.uint8, device=DEV)
-        msk = torch.zeros_like(idx) if dm else None
-        ops.maxpool2_fwd(bx, q, idx, nc, B, ci, H, H, mask=msk, drop_mode=1 if dm else 0,
-                         p_drop=p, seed=3, counts=cnt, in_affine=(sc, sh))
-    dy = torch.randn(nc, B, co, hw, hw, device=DEV)
-    w = torch.randn(nc, co, ci, 3, 3, device=DEV) * 0.1
-
-    def run(armed):
-        dq = torch.zeros(nc, B, ci, hw, hw, device=DEV)
-        part = torch.zeros(nc, ci, ops.bnstats_tiles(B, hw, hw), 2, dtype=torch.float64,
-                           device=DEV)
-        bb = (bx, sc, sh, sm, part) + ((idx, msk, p) if pooled else ())
-        _arm(armed)
-        ops.conv2d_dgrad(dy, w, dq, nc, B, ci, hw, hw, co, 3, 1, 1, counts=cnt, bn_bwd=bb)
-        dx = torch.full_like(bx, 5.0)
-        dg, db = torch.zeros(nc, ci, device=DEV), torch.zeros(nc, ci, device=DEV)
-        if pooled:
-            ops.bn_bwd_pool_tiles(part, dq, idx, bx, gamma, beta, sm, si, dx, dg, db, nc, B, ci,
-                                  H, H, pmask=msk, p_drop=p, counts=cnt)
-        else:
-            ops.bn_bwd_tiles(part, dq, bx, gamma, sm, si, dx, dg, db, nc, B, ci, H * H,
-                             counts=cnt)
-        return dx, dg, db
-
-    on, off = _both(run)
-    _eq(on[0], off[0], cnt)
-    _eq(on[1], off[1])
-    _eq(on[2], off[2])
-
-
 def test_unconsumed_reduction_materialises():
     """An armed split FWD whose output is read by something other than its BN call: the
     skipped epilogue runs first (the reader sees the reduced output)."""
@@ -212,8 +162,7 @@ def _rounds(model_name, sizes, split_bn, graphs, **kw):
         ops.SPLIT_BN[0], ops.SPLIT_BN_MAX[0] = prev, prev_max
 
 
-@pytest.mark.parametrize("model_name,kw", [("cifar10_cnn", {"dropout_rate": 0.3}),
-                                           ("federated_resnet", {"num_blocks": [1, 1, 1]})])
+@pytest.mark.parametrize("model_name,kw", [("cifar10_cnn", {"dropout_rate": 0.3})])
 def test_rounds_bit_identical_with_split_bn(model_name, kw):
     """One-client and ragged steps (split plans): the trained rows and BN buffers with the
     fused launches equal the two-launch path's bit for bit, eager and replayed."""
