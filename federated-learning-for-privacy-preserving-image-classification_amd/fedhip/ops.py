@@ -1112,6 +1112,33 @@ def fedavg_weighted_sum(rows, weights_f32, out, row_index=None, accumulate=False
     return out
 
 
+def trimmed_mean_rows(rows, out, trim, row_index=None, P=None):
+    """out[j] = mean of the C values rows[row_index[k], j] without the `trim` smallest and the
+    `trim` largest (total order -Inf < .. < -0 < +0 < .. < +Inf < NaN; sequential fp32 sum in
+    ascending order, one fp32 division; include/fedhip.h).  C = row_index.numel(), or the
+    number of rows.  trim = (C - 1) // 2 is the coordinate-wise median."""
+    require_device(rows, "rows")
+    C = rows.shape[0] if row_index is None else row_index.numel()
+    P = rows.shape[1] if P is None else P
+    call("fh_trimmed_mean_rows", ptr(rows), rows.stride(0), ptr(row_index), C, int(trim), P,
+         ptr(out), stream_handle())
+    return out
+
+
+def pairwise_sqdist(rows, row_index=None, P=None):
+    """[C, C] float64: dist[a][b] = sum_j ((double)(x_a[j] - x_b[j]))^2 over the rows selected
+    by row_index (default: all), symmetric with a zero diagonal; same bits on every run."""
+    require_device(rows, "rows")
+    C = rows.shape[0] if row_index is None else row_index.numel()
+    P = rows.shape[1] if P is None else P
+    dist = torch.empty(C, C, dtype=torch.float64, device=rows.device)
+    need = load().fh_pairwise_sqdist_workspace(C, P)
+    ws = _ws(rows.device).get(need) if need else None
+    call("fh_pairwise_sqdist", ptr(rows), rows.stride(0), ptr(row_index), C, P, ptr(ws), need,
+         ptr(dist), stream_handle())
+    return dist
+
+
 def update_stats(rows, seg_offsets, nclients):
     nseg = seg_offsets.numel() - 1
     absmax = torch.empty(nclients, nseg, dtype=torch.float32, device=rows.device)

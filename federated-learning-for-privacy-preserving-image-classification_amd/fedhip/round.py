@@ -17,6 +17,13 @@ the all-reduce differs from that loop by a few ulp; ``exact=True`` instead
 all-gathers every client's row and runs the sequential FedAvg kernel over all
 clients in global client order on every rank (fedavg.py:278-285 bit for bit, at
 C x P floats of gather traffic per rank instead of one P-float all-reduce).
+
+``aggregator`` (a src.aggregation.robust rule: trimmed mean, median, Krum) replaces the FedAvg
+of the PARAMETER rows by the rule's ``aggregate_packed`` over the same rows: this rank's on one
+rank, the all-gathered rows of every client (global client order) with ``exact=True`` on
+several.  A robust rule is not a sum, so it cannot be all-reduced: several ranks without
+``exact`` are refused at construction.  The BN running statistics (``global_bufs``) keep the
+plain FedAvg.  With ``aggregator=None`` nothing changes.
 """
 from __future__ import annotations
 
@@ -47,7 +54,7 @@ class RankRound:
     def __init__(self, template_model, all_train_sizes: Sequence[int], my_clients: Sequence[int],
                  epochs: int = 1, batch: int = 32, device="cuda", dp: Optional[DPConfig] = None,
                  group=None, lanes=None, compression=None, transform=None, dp_seed=None,
-                 shuffle_seed=None, exact=False):
+                 shuffle_seed=None, exact=False, aggregator=None):
         self.device = torch.device(device)
         self._template = template_model
         self.B, self.epochs, self.dp, self.group = batch, epochs, dp, group
@@ -59,6 +66,11 @@ class RankRound:
         steps = [epochs * math.ceil(self.all_sizes[k] / batch) for k in self.slots]
         self.distributed = group is not None or (dist.is_available() and dist.is_initialized())
         self.rank = dist.get_rank(group) if self.distributed else 0
+        self.aggregator = aggregator
+        if aggregator is not None and not exact and self.distributed \
+                and dist.get_world_size(group) > 1:
+            raise ops.FedHipError("a robust aggregator over several ranks needs exact=True: "
+                                  "the rule is not a sum and cannot be all-reduced")
         self.trainer = LanedTrainer(template_model, steps or [0], batch=batch, device=self.device,
                                     lanes=lanes, salt=self.rank)
         if self.slots:  # dropout / augmentation keyed by global client id (not rank / lane)
@@ -80,6 +92,9 @@ class RankRound:
                                 device=self.device)
         self.rows = torch.tensor([self.slot_of[k] for k in self.clients], dtype=torch.int32,
                                  device=self.device)
+        # what a robust aggregator is handed on one rank: its clients' rows and sample counts
+        self._agg_rows = [self.slot_of[k] for k in self.clients]
+        self._agg_samples = [processed[k] for k in self.clients]
         # update-level DP noise: Philox keyed by (round key, global client id, element), so
         # no two clients — on any rank or lane — ever draw the same noise; the round key
         # comes from a secret base seed (os.urandom) unless the caller fixes one (tests /
@@ -139,13 +154,15 @@ class RankRound:
         self._x_w32 = torch.tensor([self.weights[k] for k in order], dtype=torch.float32,
                                    device=self.device)
         self._x_idx = torch.tensor([pos[k] for k in order], dtype=torch.int32, device=self.device)
+        self._x_rows = [pos[k] for k in order]
+        self._x_samples = [self.epochs * self.all_sizes[k] for k in order]
         self._x_mine = torch.tensor([self.slot_of[k] for k in self.clients], dtype=torch.int64,
                                     device=self.device)
         self._x_buf = {}
 
-    def _exact_fedavg(self, rows, n, out):
-        """out = sum over ALL clients, in global client order, of fl32(w_k) * row_k: this
-        rank's rows (client-list order, zero padded) all-gathered, then fh_fedavg_weighted_sum."""
+    def _exact_gather(self, rows, n):
+        """[world * maxS, n]: this rank's rows (client-list order, zero padded) all-gathered;
+        global client k sits at row _x_rows[k]."""
         world, maxS = self._x_world, self._x_maxS
         buf = self._x_buf.get(n)
         if buf is None:
@@ -156,7 +173,12 @@ class RankRound:
         if S:
             torch.index_select(rows[:, :n], 0, self._x_mine, out=send[:S])
         dist.all_gather(list(recv.unbind(0)), send, group=self.group)
-        ops.fedavg_weighted_sum(recv.view(world * maxS, n), self._x_w32, out,
+        return recv.view(world * maxS, n)
+
+    def _exact_fedavg(self, rows, n, out):
+        """out = sum over ALL clients, in global client order, of fl32(w_k) * row_k: the
+        all-gathered rows, then fh_fedavg_weighted_sum."""
+        ops.fedavg_weighted_sum(self._exact_gather(rows, n), self._x_w32, out,
                                 row_index=self._x_idx, P=n)
 
     def client_shuffle_seed(self, seed: int, client: int) -> int:
@@ -197,17 +219,27 @@ class RankRound:
                           base=self.global_flat.view(1, -1).expand(S, -1))
         distributed = self.distributed
         if self.exact:  # bit-exact multi-rank FedAvg: all-gather + one sequential sum
-            self._exact_fedavg(tr.params, self.P, self.global_flat)
+            if self.aggregator is None:
+                self._exact_fedavg(tr.params, self.P, self.global_flat)
+            else:  # the rule over every client's row, in global client order, on every rank
+                self.aggregator.aggregate_packed(self._exact_gather(tr.params, self.P),
+                                                 self._x_samples, row_index=self._x_rows,
+                                                 out=self.global_flat)
             if self.Q:
                 self._exact_fedavg(tr.bufs, self.Q, self.global_bufs)
             self.round_index += 1
             self._host_timing(_t)
             return metrics
         # FedAvg: this rank's partial sum in client-list order, then RCCL all-reduce.
-        ops.fedavg_weighted_sum(tr.params, self.w32, self.partial, row_index=self.rows, P=self.P)
-        if distributed:
-            dist.all_reduce(self.partial, op=dist.ReduceOp.SUM, group=self.group)
-        self.global_flat.copy_(self.partial)
+        if self.aggregator is None:
+            ops.fedavg_weighted_sum(tr.params, self.w32, self.partial, row_index=self.rows,
+                                    P=self.P)
+            if distributed:
+                dist.all_reduce(self.partial, op=dist.ReduceOp.SUM, group=self.group)
+            self.global_flat.copy_(self.partial)
+        else:  # one rank (checked at construction): the rule over this rank's rows
+            self.aggregator.aggregate_packed(tr.params[:, :self.P], self._agg_samples,
+                                             row_index=self._agg_rows, out=self.global_flat)
         if self.Q:
             ops.fedavg_weighted_sum(tr.bufs, self.w32, self.global_bufs, row_index=self.rows,
                                     P=self.Q)

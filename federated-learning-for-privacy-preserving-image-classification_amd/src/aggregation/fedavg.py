@@ -191,19 +191,17 @@ class FedAvgAggregator(AggregationServiceInterface):
             return [1.0 / len(weights)] * len(weights)
         return [w / total for w in weights]
 
-    def _weighted_average(self, updates: List[ModelUpdate], weights: List[float]) -> ModelWeights:
-        """Device-packed: client rows [C, P] -> one fused FedAvg launch -> layer views.
-        Layers missing from update 0 are ignored; layers missing from a later update
-        contribute nothing for that client (reference :278-287)."""
+    def _pack_updates(self, updates: List[ModelUpdate]):
+        """Client rows [C, P] on the device in client-list order, plus the layer names,
+        offsets and sizes of update 0.  Layers missing from update 0 are ignored; layers
+        missing from a later update contribute zeros for that client (reference :278-287)."""
         if not updates:
             raise FedAvgError("No updates to aggregate")
         ref = updates[0].model_weights
         names = list(ref)
         sizes = [ref[n].numel() for n in names]
         offs = np.cumsum([0] + sizes).tolist()
-        P = offs[-1]
-        dev = self.device
-        rows = torch.zeros(len(updates), P, dtype=torch.float32, device=dev)
+        rows = torch.zeros(len(updates), offs[-1], dtype=torch.float32, device=self.device)
         for k, u in enumerate(updates):
             for n, o, s in zip(names, offs, sizes):
                 t = u.model_weights.get(n)
@@ -212,11 +210,20 @@ class FedAvgAggregator(AggregationServiceInterface):
             for n in u.model_weights:
                 if n not in ref:
                     logger.warning(f"Layer {n} not found in reference model")
-        w32 = torch.tensor(weights, dtype=torch.float32, device=dev)
-        out = torch.empty(P, dtype=torch.float32, device=dev)
-        ops.fedavg_weighted_sum(rows, w32, out)
+        return rows, names, offs, sizes
+
+    @staticmethod
+    def _unpack_row(out: torch.Tensor, ref: ModelWeights, names, offs, sizes) -> ModelWeights:
         return {n: out[o:o + s].view(ref[n].shape).to(ref[n].device)
                 for n, o, s in zip(names, offs, sizes)}
+
+    def _weighted_average(self, updates: List[ModelUpdate], weights: List[float]) -> ModelWeights:
+        """Device-packed: client rows [C, P] -> one fused FedAvg launch -> layer views."""
+        rows, names, offs, sizes = self._pack_updates(updates)
+        w32 = torch.tensor(weights, dtype=torch.float32, device=self.device)
+        out = torch.empty(offs[-1], dtype=torch.float32, device=self.device)
+        ops.fedavg_weighted_sum(rows, w32, out)
+        return self._unpack_row(out, updates[0].model_weights, names, offs, sizes)
 
     def _record_aggregation_stats(self, updates, weights, total_samples, avg_training_loss,
                                   aggregation_time):

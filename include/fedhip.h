@@ -69,6 +69,38 @@ int fh_update_stats(const float* rows, int64_t row_stride, int32_t num_clients,
                     const int64_t* seg_offsets, int32_t nseg, float* seg_absmax,
                     int32_t* seg_nonfinite, void* stream);
 
+/* ---------------- Byzantine-robust aggregation (no reference counterpart) --
+ * Coordinate-wise trimmed mean (Yin et al. 2018).  For each coordinate j independently take
+ * the C values rows[idx[k]*row_stride + j] (row_index may be NULL: identity) and order them
+ * by the total order on the 32-bit key
+ *     key(x) = bits(x) ^ (sign(x) ? 0xFFFFFFFF : 0x80000000),  compared as unsigned,
+ * after every NaN (either sign, any payload) has been mapped to one key above +Inf:
+ *     -Inf < ... < -0 < +0 < ... < +Inf < NaN.
+ * With the sorted values s[0..C-1],
+ *     out[j] = (((s[t] + s[t+1]) + ...) + s[C-1-t]) / (float)(C - 2t),   t = trim,
+ * fp32 additions in ascending sorted order, one IEEE fp32 division, no FMA; a NaN result is
+ * written as the one quiet NaN 0x7FC00000.  The result does not depend on the row order,
+ * bit for bit.  Up to `trim` NaN or +-Inf rows per coordinate are discarded; more propagate.
+ * The median is trim = (C-1)/2: s[mid] / 1.0f for odd C, (s[C/2-1] + s[C/2]) / 2.0f for even.
+ * Requires 1 <= C <= 64 and 0 <= 2*trim < C (FH_E_INVALID otherwise); P == 0 is a no-op.
+ * No workspace.  16-byte loads when row_stride % 4 == 0 and rows / out are 16-byte aligned;
+ * a scalar path with the same bits covers everything else and the P % 4 tail. */
+int fh_trimmed_mean_rows(const float* rows, int64_t row_stride, const int32_t* row_index,
+                         int32_t num_clients, int32_t trim, int64_t P, float* out, void* stream);
+
+/* Pairwise squared distances of client rows (the input of Krum / multi-Krum, Blanchard et
+ * al. 2017):  dist[a][b] = sum_j ((double)(x_a[j] - x_b[j]))^2  with x_k = rows[idx[k]*
+ * row_stride + .]: one rounded fp32 subtraction, square and sum in fp64, computed from the
+ * differences directly (never ||a||^2 + ||b||^2 - 2ab, which cancels for rows that sit
+ * within one update of each other).  dist: device double[C][C], symmetric, zero diagonal.
+ * No atomics: each workgroup writes the partials of its chunk of coordinates for all
+ * C(C-1)/2 pairs to `workspace` (>= fh_pairwise_sqdist_workspace(C, P) bytes) and a second
+ * launch adds them in chunk order, so the bits are the same on every run.  2 <= C <= 64. */
+size_t fh_pairwise_sqdist_workspace(int32_t num_clients, int64_t P);
+int fh_pairwise_sqdist(const float* rows, int64_t row_stride, const int32_t* row_index,
+                       int32_t num_clients, int64_t P, void* workspace, size_t ws_bytes,
+                       double* dist, void* stream);
+
 /* ---------------- update-level DP (privacy.py:107-144, 183-254) ----------
  * delta = fl32(local - global) (global may be NULL: delta = local).
  * seg_sqnorm[z*nseg+t] = sum over segment t of delta^2, accumulated in fp64. */
