@@ -1139,6 +1139,64 @@ def pairwise_sqdist(rows, row_index=None, P=None):
     return dist
 
 
+def _terms(term_keys, term_signs, shape):
+    """(keys ptr, signs ptr, nterms) of a term list: int64 keys (the uint64's bits) and int32
+    signs, contiguous, shaped `shape` + [nterms]; None = no terms."""
+    if term_keys is None and term_signs is None:
+        return None, None, 0
+    if term_keys is None or term_signs is None:
+        raise FedHipError("secagg: term_keys and term_signs go together")
+    want = tuple(shape) + (term_keys.shape[-1],)
+    for t, dt, what in ((term_keys, torch.int64, "term_keys"), (term_signs, torch.int32,
+                                                                 "term_signs")):
+        require_device(t, what)
+        if t.dtype != dt or tuple(t.shape) != want or not t.is_contiguous():
+            raise FedHipError(f"secagg: {what} must be a contiguous {dt} tensor of shape {want} "
+                              f"(got {t.dtype} {tuple(t.shape)})")
+    return ptr(term_keys), ptr(term_signs), want[-1]
+
+
+def secagg_encode_mask_rows(rows, out, frac_bits, qmax, term_keys=None, term_signs=None, nonce=0,
+                            weights=None, row_index=None, clipped=None, P=None):
+    """out[z] (int32 rows holding the bits of elements of Z/2^32) = the fixed-point code of
+    [weights[z] *] rows[row_index[z]] at `frac_bits` fractional bits, saturated to +-qmax, plus
+    sum_t term_signs[z, t] * mask(term_keys[z, t], nonce) mod 2^32 (include/fedhip.h).
+    term_keys: int64 [num_rows, nterms] (the uint64 keys' bits), term_signs: int32 likewise.
+    clipped (int32 [num_rows]) is ADDED to: NaN, and values beyond +-qmax, per row."""
+    require_device(rows, "rows")
+    require_device(out, "out")
+    if out.dtype != torch.int32 or rows.dtype != torch.float32:
+        raise FedHipError("secagg: rows must be float32 and out int32")
+    Z = rows.shape[0] if row_index is None else row_index.numel()
+    P = rows.shape[1] if P is None else P
+    if P and (rows.stride(1) != 1 or out.stride(1) != 1):
+        raise FedHipError("secagg: rows and out need unit column stride")
+    kp, sp, nterms = _terms(term_keys, term_signs, (Z,))
+    call("fh_secagg_encode_mask_rows", ptr(rows), rows.stride(0), ptr(row_index), ptr(weights), Z,
+         P, int(frac_bits), int(qmax), kp, sp, nterms, int(nonce) & 0xFFFFFFFFFFFFFFFF, ptr(out),
+         out.stride(0), ptr(clipped), stream_handle())
+    return out
+
+
+def secagg_sum_decode(masked, frac_bits, term_keys=None, term_signs=None, nonce=0, row_index=None,
+                      out=None, sum_out=None, P=None):
+    """sum_out (int32 [P], ring bits) = sum of the rows masked[row_index[k]] minus
+    sum_t term_signs[t] * mask(term_keys[t], nonce) mod 2^32;  out (fp32 [P]) = that sum read
+    as int32, times 2^-frac_bits.  At least one of out / sum_out."""
+    require_device(masked, "masked")
+    if masked.dtype != torch.int32:
+        raise FedHipError("secagg: masked rows must be int32")
+    K = masked.shape[0] if row_index is None else row_index.numel()
+    P = masked.shape[1] if P is None else P
+    if P and masked.stride(1) != 1:
+        raise FedHipError("secagg: masked rows need unit column stride")
+    kp, sp, nterms = _terms(term_keys, term_signs, ())
+    call("fh_secagg_sum_decode", ptr(masked), masked.stride(0), ptr(row_index), K, P, kp, sp,
+         nterms, int(nonce) & 0xFFFFFFFFFFFFFFFF, int(frac_bits), ptr(out), ptr(sum_out),
+         stream_handle())
+    return out, sum_out
+
+
 def update_stats(rows, seg_offsets, nclients):
     nseg = seg_offsets.numel() - 1
     absmax = torch.empty(nclients, nseg, dtype=torch.float32, device=rows.device)

@@ -101,6 +101,45 @@ int fh_pairwise_sqdist(const float* rows, int64_t row_stride, const int32_t* row
                        int32_t num_clients, int64_t P, void* workspace, size_t ws_bytes,
                        double* dist, void* stream);
 
+/* ---------------- secure aggregation (no reference counterpart) ------------
+ * Pairwise-masked fixed-point rows in the ring Z/2^32 (Bonawitz et al., CCS 2017).  Both entry
+ * points work on mask terms (key: uint64, sign: int32; > 0 adds, < 0 subtracts, 0 skips the
+ * term).  With the launch-wide `nonce`, a term's mask word for coordinate j is
+ *     m(key, j) = word (j % 4) of Philox4x32-10(seed = key, ctr_hi = nonce, ctr_lo = j / 4),
+ * words in the order .x .y .z .w.  Who shares which key is the caller's protocol.
+ *
+ * fh_secagg_encode_mask_rows: for each row z < num_rows and coordinate j < P, with
+ * x = rows[idx[z]*row_stride + j] (row_index may be NULL: identity),
+ *     v = weights ? fl32(weights[z] * x) : x          one rounded fp32 multiply, never fused
+ *     r = rint((double)v * 2^frac_bits)               exact product, round to nearest even
+ *     NaN -> r = 0;  r > qmax -> qmax;  r < -qmax -> -qmax;  each adds 1 to clipped[z]
+ *     out[z*out_stride + j] = (uint32)(int32)r + sum_t sign[z][t] * m(key[z][t], j)  mod 2^32
+ * term_keys / term_signs: device [num_rows][nterms]; weights: device float[num_rows] or NULL;
+ * clipped: device int32[num_rows] or NULL, ADDED to (the caller zeroes it) with one integer
+ * atomic per workgroup, so the count is the same on every run.  Requires 0 <= frac_bits <= 30,
+ * 1 <= qmax <= 2^31 - 1, 0 <= nterms <= 64, 1 <= num_rows (FH_E_INVALID otherwise); P == 0 is
+ * a no-op.  No workspace.  16-byte loads and stores when both strides % 4 == 0 and rows / out
+ * are 16-byte aligned; a scalar path with the same bits covers everything else and the P % 4
+ * tail. */
+int fh_secagg_encode_mask_rows(const float* rows, int64_t row_stride, const int32_t* row_index,
+                               const float* weights, int32_t num_rows, int64_t P,
+                               int32_t frac_bits, int32_t qmax, const uint64_t* term_keys,
+                               const int32_t* term_signs, int32_t nterms, uint64_t nonce,
+                               uint32_t* out, int64_t out_stride, int32_t* clipped, void* stream);
+
+/* The server's side: sum the masked rows, remove the terms that did not cancel (pair masks
+ * between surviving and dropped clients, the survivors' self masks) and decode:
+ *     acc[j]     = sum_k masked[idx[k]*stride + j] - sum_t sign[t] * m(key[t], j)   mod 2^32
+ *     sum_out[j] = acc[j]
+ *     out[j]     = (float)((double)(int32)acc[j] * 2^-frac_bits)      one rounding, to fp32
+ * term_keys / term_signs: device [nterms], nterms >= 0; out (fp32) and sum_out (uint32) may
+ * each be NULL but not both; 1 <= num_rows; 0 <= frac_bits <= 30; P == 0 is a no-op.  Sums in
+ * the ring do not depend on the order of rows or terms.  Paths as above. */
+int fh_secagg_sum_decode(const uint32_t* masked, int64_t stride, const int32_t* row_index,
+                         int32_t num_rows, int64_t P, const uint64_t* term_keys,
+                         const int32_t* term_signs, int32_t nterms, uint64_t nonce,
+                         int32_t frac_bits, float* out, uint32_t* sum_out, void* stream);
+
 /* ---------------- update-level DP (privacy.py:107-144, 183-254) ----------
  * delta = fl32(local - global) (global may be NULL: delta = local).
  * seg_sqnorm[z*nseg+t] = sum over segment t of delta^2, accumulated in fp64. */
