@@ -1125,6 +1125,40 @@ def trimmed_mean_rows(rows, out, trim, row_index=None, P=None):
     return out
 
 
+SOPT_MOMENTUM, SOPT_ADAGRAD, SOPT_ADAM, SOPT_YOGI = range(4)  # FH_SOPT_* of include/fedhip.h
+
+
+def server_opt_step(rows, global_, m, v, rule, server_lr, beta1, beta2, tau, weights_f32=None,
+                    row_index=None, P=None):
+    """One adaptive server-optimizer step (FedAvgM / FedAdagrad / FedAdam / FedYogi; the
+    arithmetic is defined in include/fedhip.h): global_, m and v (fp32 [P], contiguous) are
+    updated in place from the pseudo-gradient  aggregate - global_.  With `weights_f32` the
+    aggregate is sum_k fl32(w_k) * rows[row_index[k]], formed in the same launch exactly as
+    fedavg_weighted_sum forms it; without, rows holds ONE row (or row_index picks one) that is
+    the aggregate already.  v may be None for SOPT_MOMENTUM.  Returns global_."""
+    require_device(rows, "rows")
+    for t, what in ((global_, "global_"), (m, "m"), (v, "v")):
+        if t is not None:
+            require_device(t, what)
+    if weights_f32 is not None:
+        C = weights_f32.numel()
+    else:
+        C = rows.shape[0] if row_index is None else row_index.numel()
+    P = rows.shape[1] if P is None else P
+    if rows.dtype != torch.float32 or P > rows.shape[1] or (P and rows.stride(1) != 1):
+        raise FedHipError(f"server_opt: rows must be float32 with unit column stride and at "
+                          f"least P={P} columns (got {rows.dtype} {tuple(rows.shape)})")
+    for t, what in ((global_, "global_"), (m, "m"), (v, "v")):
+        if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()
+                              or t.numel() < P):
+            raise FedHipError(f"server_opt: {what} must be a contiguous float32 vector of at "
+                              f"least P={P} elements (got {t.dtype} {tuple(t.shape)})")
+    call("fh_server_opt_step", ptr(rows), rows.stride(0), ptr(row_index), ptr(weights_f32), C, P,
+         ptr(global_), ptr(m), ptr(v), int(rule), float(server_lr), float(beta1), float(beta2),
+         float(tau), stream_handle())
+    return global_
+
+
 def pairwise_sqdist(rows, row_index=None, P=None):
     """[C, C] float64: dist[a][b] = sum_j ((double)(x_a[j] - x_b[j]))^2 over the rows selected
     by row_index (default: all), symmetric with a zero diagonal; same bits on every run."""

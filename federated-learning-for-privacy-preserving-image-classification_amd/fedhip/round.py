@@ -24,6 +24,17 @@ rank, the all-gathered rows of every client (global client order) with ``exact=T
 several.  A robust rule is not a sum, so it cannot be all-reduced: several ranks without
 ``exact`` are refused at construction.  The BN running statistics (``global_bufs``) keep the
 plain FedAvg.  With ``aggregator=None`` nothing changes.
+
+``server_opt`` (a src.aggregation.fedopt.ServerOptimizer: FedAvgM, FedAdagrad, FedAdam, FedYogi)
+replaces the assignment of the aggregate to the global PARAMETER vector by one server-optimizer
+step toward it.  One rank without ``aggregator``: one fused launch over the rank's rows (the
+weighted sum never leaves registers).  Every other path forms its aggregate in ``partial`` as
+before (the all-reduced sum, the exact-mode FedAvg, the robust rule) and a single-row step
+follows; every rank holds the same state and runs the same deterministic kernel on the same
+aggregate, so the ranks stay bit-identical without a broadcast.  A ``server_opt`` whose ``base``
+is a robust rule uses that rule as ``aggregator``; given together with ``aggregator=`` it is
+refused.  The BN running statistics keep the plain FedAvg.  With ``server_opt=None`` nothing
+changes.
 """
 from __future__ import annotations
 
@@ -54,7 +65,7 @@ class RankRound:
     def __init__(self, template_model, all_train_sizes: Sequence[int], my_clients: Sequence[int],
                  epochs: int = 1, batch: int = 32, device="cuda", dp: Optional[DPConfig] = None,
                  group=None, lanes=None, compression=None, transform=None, dp_seed=None,
-                 shuffle_seed=None, exact=False, aggregator=None):
+                 shuffle_seed=None, exact=False, aggregator=None, server_opt=None):
         self.device = torch.device(device)
         self._template = template_model
         self.B, self.epochs, self.dp, self.group = batch, epochs, dp, group
@@ -66,7 +77,12 @@ class RankRound:
         steps = [epochs * math.ceil(self.all_sizes[k] / batch) for k in self.slots]
         self.distributed = group is not None or (dist.is_available() and dist.is_initialized())
         self.rank = dist.get_rank(group) if self.distributed else 0
-        self.aggregator = aggregator
+        if server_opt is not None and not server_opt.plain_base:
+            if aggregator is not None:
+                raise ops.FedHipError("server_opt has a robust base and aggregator= is given "
+                                      "too: ambiguous, pass the rule once")
+            aggregator = server_opt.base
+        self.aggregator, self.server_opt = aggregator, server_opt
         if aggregator is not None and not exact and self.distributed \
                 and dist.get_world_size(group) > 1:
             raise ops.FedHipError("a robust aggregator over several ranks needs exact=True: "
@@ -218,13 +234,18 @@ class RankRound:
             compress_rows(self._cplan, self.compression, tr.params, S,
                           base=self.global_flat.view(1, -1).expand(S, -1))
         distributed = self.distributed
+        sopt = self.server_opt
+        # with a server optimizer the aggregate lands in `partial` and the global steps to it
+        agg_out = self.global_flat if sopt is None else self.partial
         if self.exact:  # bit-exact multi-rank FedAvg: all-gather + one sequential sum
             if self.aggregator is None:
-                self._exact_fedavg(tr.params, self.P, self.global_flat)
+                self._exact_fedavg(tr.params, self.P, agg_out)
             else:  # the rule over every client's row, in global client order, on every rank
                 self.aggregator.aggregate_packed(self._exact_gather(tr.params, self.P),
                                                  self._x_samples, row_index=self._x_rows,
-                                                 out=self.global_flat)
+                                                 out=agg_out)
+            if sopt is not None:
+                sopt.step_vector(self.partial, self.global_flat)
             if self.Q:
                 self._exact_fedavg(tr.bufs, self.Q, self.global_bufs)
             self.round_index += 1
@@ -232,14 +253,22 @@ class RankRound:
             return metrics
         # FedAvg: this rank's partial sum in client-list order, then RCCL all-reduce.
         if self.aggregator is None:
-            ops.fedavg_weighted_sum(tr.params, self.w32, self.partial, row_index=self.rows,
-                                    P=self.P)
-            if distributed:
-                dist.all_reduce(self.partial, op=dist.ReduceOp.SUM, group=self.group)
-            self.global_flat.copy_(self.partial)
+            if sopt is not None and not distributed:  # weighted sum + step, one launch
+                sopt.step_rows(tr.params, self.w32, self.global_flat, self.rows)
+            else:
+                ops.fedavg_weighted_sum(tr.params, self.w32, self.partial, row_index=self.rows,
+                                        P=self.P)
+                if distributed:
+                    dist.all_reduce(self.partial, op=dist.ReduceOp.SUM, group=self.group)
+                if sopt is None:
+                    self.global_flat.copy_(self.partial)
+                else:
+                    sopt.step_vector(self.partial, self.global_flat)
         else:  # one rank (checked at construction): the rule over this rank's rows
             self.aggregator.aggregate_packed(tr.params[:, :self.P], self._agg_samples,
-                                             row_index=self._agg_rows, out=self.global_flat)
+                                             row_index=self._agg_rows, out=agg_out)
+            if sopt is not None:
+                sopt.step_vector(self.partial, self.global_flat)
         if self.Q:
             ops.fedavg_weighted_sum(tr.bufs, self.w32, self.global_bufs, row_index=self.rows,
                                     P=self.Q)

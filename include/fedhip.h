@@ -140,6 +140,40 @@ int fh_secagg_sum_decode(const uint32_t* masked, int64_t stride, const int32_t* 
                          const int32_t* term_signs, int32_t nterms, uint64_t nonce,
                          int32_t frac_bits, float* out, uint32_t* sum_out, void* stream);
 
+/* ---------------- adaptive server optimizers (no reference counterpart) ----
+ * Reddi et al., "Adaptive Federated Optimization" (ICLR 2021): the server steps the global
+ * model along the pseudo-gradient d = aggregate - global with moments m, v kept across rounds.
+ * Per coordinate j; every operation is one rounded fp32 operation, never fused; sqrtf and / are
+ * IEEE correctly rounded; denormals are kept:
+ *     a    = weights ? (((0 + w[0]*x_0[j]) + w[1]*x_1[j]) + ...)   exactly fh_fedavg_weighted_sum
+ *                    : x_0[j]          weights NULL: num_clients must be 1, the row IS the aggregate
+ *            x_k = rows[idx[k]*row_stride + j], row_index NULL = identity
+ *     d    = a - g                                             g = global[j]
+ *     omb1 = 1.0f - beta1,  omb2 = 1.0f - beta2                computed once, in fp32
+ *     MOMENTUM: m' = (beta1*m) + d          g' = g + server_lr*m'     v not read or written (may be NULL)
+ *     others:   m' = (beta1*m) + (omb1*d)
+ *               d2 = d*d
+ *       ADAGRAD v' = v + d2
+ *       ADAM    v' = (beta2*v) + (omb2*d2)
+ *       YOGI    t  = v - d2;  s = t>0 ? 1.0f : t<0 ? -1.0f : 0.0f (NaN t: 0);  v' = v - ((omb2*d2)*s)
+ *               g' = g + server_lr * ( m' / (sqrtf(v') + tau) )
+ * g', m' and v' are stored in place; any NaN is stored as the one quiet NaN 0x7FC00000.  No bias
+ * correction (the paper uses none).  The initial state is the caller's: m = 0, v = tau^2.
+ * FH_E_INVALID for: rule outside 0..3; num_clients < 1; weights == NULL with num_clients != 1;
+ * P < 0; null rows / global / m; null v for rules 1..3; tau < 0 or a non-finite server_lr /
+ * beta / tau.  P == 0 is a no-op.  No workspace.  16-byte loads and stores when row_stride % 4
+ * == 0 and rows, global, m and v are 16-byte aligned; a scalar path with the same bits covers
+ * everything else and the P % 4 tail.  Reads (C+3)*P floats and writes 3*P ((C+2)*P and 2*P
+ * for MOMENTUM). */
+#define FH_SOPT_MOMENTUM 0   /* FedAvgM  */
+#define FH_SOPT_ADAGRAD  1   /* FedAdagrad */
+#define FH_SOPT_ADAM     2   /* FedAdam  */
+#define FH_SOPT_YOGI     3   /* FedYogi  */
+int fh_server_opt_step(const float* rows, int64_t row_stride, const int32_t* row_index,
+                       const float* weights, int32_t num_clients, int64_t P,
+                       float* global, float* m, float* v, int32_t rule,
+                       float server_lr, float beta1, float beta2, float tau, void* stream);
+
 /* ---------------- update-level DP (privacy.py:107-144, 183-254) ----------
  * delta = fl32(local - global) (global may be NULL: delta = local).
  * seg_sqnorm[z*nseg+t] = sum over segment t of delta^2, accumulated in fp64. */
