@@ -1159,6 +1159,113 @@ def server_opt_step(rows, global_, m, v, rule, server_lr, beta1, beta2, tau, wei
     return global_
 
 
+# ------------------------------------------------------------------ central DP-FedAvg
+# FH_DPFA_* of include/fedhip.h: the device state block, the Philox stream words, the flags
+DPFA_STATE_DOUBLES = 8
+DPFA_CLIP, DPFA_SIGMA, DPFA_BITSUM, DPFA_BBAR, DPFA_NEXT, DPFA_PREV = range(6)
+DPFA_STREAM_NOISE, DPFA_STREAM_BIT = (1 << 64) - 1, (1 << 64) - 2
+DPFA_ROWS_ARE_DELTAS, DPFA_NO_GLOBAL_ADD = 1, 2
+
+
+def _dpfa_rows(rows, row_index, P, what):
+    require_device(rows, "rows")
+    if row_index is not None:
+        require_device(row_index, "row_index")
+        if row_index.dtype != torch.int32 or not row_index.is_contiguous():
+            raise FedHipError(f"{what}: row_index must be a contiguous int32 vector")
+    if rows.dim() != 2:
+        raise FedHipError(f"{what}: rows must be a float32 [clients, >= P] matrix (got shape "
+                          f"{tuple(rows.shape)})")
+    C = rows.shape[0] if row_index is None else row_index.numel()
+    P = rows.shape[1] if P is None else P
+    if rows.dtype != torch.float32 or P > rows.shape[1] or (P and rows.stride(1) != 1):
+        raise FedHipError(f"{what}: rows must be float32 [clients, >= P={P}] with unit column "
+                          f"stride (got {rows.dtype} {tuple(rows.shape)})")
+    return C, P
+
+
+def _dpfa_vec(t, dtype, n, what, name):
+    if t is None:
+        return
+    require_device(t, name)
+    if t.dtype != dtype or not t.is_contiguous() or t.numel() < n:
+        raise FedHipError(f"{what}: {name} must be a contiguous {dtype} vector of at least {n} "
+                          f"elements (got {t.dtype} {tuple(t.shape)})")
+
+
+def dpfa_row_sqnorm(rows, global_=None, row_index=None, P=None, out=None):
+    """float64 [C]: out[k] = sum_j (double)fl32(rows[row_index[k], j] - global_[j])^2 over the
+    whole row (global_ None: the rows are deltas); fp64 sums in an order fixed by P and the
+    alignment, the same bits on every run (include/fedhip.h)."""
+    C, P = _dpfa_rows(rows, row_index, P, "dpfa_row_sqnorm")
+    _dpfa_vec(global_, torch.float32, P, "dpfa_row_sqnorm", "global_")
+    if out is None:
+        out = torch.empty(C, dtype=torch.float64, device=rows.device)
+    _dpfa_vec(out, torch.float64, C, "dpfa_row_sqnorm", "out")
+    need = load().fh_dpfa_row_sqnorm_workspace(C, P)
+    ws = _ws(rows.device).get(need) if need else None
+    call("fh_dpfa_row_sqnorm", ptr(rows), rows.stride(0), ptr(row_index), ptr(global_), C, P,
+         ptr(ws), need, ptr(out), stream_handle())
+    return out
+
+
+def dpfa_clip_coef(sqnorm, state, total_clients, z_delta, scale=None, bits=None, sigma=None):
+    """(scale fp32 [C], bits int32 [C], sigma fp32 [1]) from the squared norms and the clip
+    norm state[DPFA_CLIP]: bits = n <= C_t, scale = fl32(fl32(min(1, C_t/n)) * fl32(1/m)),
+    sigma = fl32(z_delta * C_t / m); state[DPFA_SIGMA] and state[DPFA_BITSUM] are set."""
+    require_device(sqnorm, "sqnorm")
+    C, dev = sqnorm.numel(), sqnorm.device
+    _dpfa_vec(sqnorm, torch.float64, C, "dpfa_clip_coef", "sqnorm")
+    _dpfa_vec(state, torch.float64, DPFA_STATE_DOUBLES, "dpfa_clip_coef", "state")
+    scale = torch.empty(C, dtype=torch.float32, device=dev) if scale is None else scale
+    bits = torch.empty(C, dtype=torch.int32, device=dev) if bits is None else bits
+    sigma = torch.empty(1, dtype=torch.float32, device=dev) if sigma is None else sigma
+    _dpfa_vec(scale, torch.float32, C, "dpfa_clip_coef", "scale")
+    _dpfa_vec(bits, torch.int32, C, "dpfa_clip_coef", "bits")
+    _dpfa_vec(sigma, torch.float32, 1, "dpfa_clip_coef", "sigma")
+    call("fh_dpfa_clip_coef", ptr(sqnorm), C, int(total_clients), float(z_delta), ptr(state),
+         ptr(scale), ptr(bits), ptr(sigma), stream_handle())
+    return scale, bits, sigma
+
+
+def dpfa_clip_update(state, total_clients, target_quantile, clip_lr, bit_noise, seed=0,
+                     bit_sum=None):
+    """The geometric clip-norm update on the device: state[DPFA_CLIP] *= exp(-clip_lr * (bbar -
+    target_quantile)), bbar = (bit_sum + bit_noise * xi) / m.  bit_sum: a device float64 of
+    one element (default: this rank's, state[DPFA_BITSUM])."""
+    _dpfa_vec(state, torch.float64, DPFA_STATE_DOUBLES, "dpfa_clip_update", "state")
+    if state is None:
+        raise FedHipError("dpfa_clip_update: state is None")
+    if bit_sum is None:
+        bit_sum = state[DPFA_BITSUM:DPFA_BITSUM + 1]
+    _dpfa_vec(bit_sum, torch.float64, 1, "dpfa_clip_update", "bit_sum")
+    call("fh_dpfa_clip_update", ptr(state), ptr(bit_sum), int(total_clients),
+         float(target_quantile), float(clip_lr), float(bit_noise),
+         int(seed) & 0xFFFFFFFFFFFFFFFF, stream_handle())
+    return state
+
+
+def dpfa_clip_sum(rows, scale, out, global_=None, row_index=None, sigma=None, noise=None, seed=0,
+                  stream_hi=DPFA_STREAM_NOISE, rows_are_deltas=False, add_global=True, P=None):
+    """out = [global_ +] ((sum_k scale[k] * d_k) [+ noise]), d_k = rows[row_index[k]] - global_
+    (rows_are_deltas, or no global_: the row itself); sequential fp32, no FMA.  noise: the
+    injected fp32 [P] vector, else sigma[0] * N(0, 1) from Philox(seed, stream_hi) when sigma
+    (device fp32 [1]) is given, else none.  out may alias global_ (include/fedhip.h)."""
+    C, P = _dpfa_rows(rows, row_index, P, "dpfa_clip_sum")
+    require_device(out, "out")
+    _dpfa_vec(scale, torch.float32, C, "dpfa_clip_sum", "scale")
+    _dpfa_vec(out, torch.float32, P, "dpfa_clip_sum", "out")
+    _dpfa_vec(global_, torch.float32, P, "dpfa_clip_sum", "global_")
+    _dpfa_vec(sigma, torch.float32, 1, "dpfa_clip_sum", "sigma")
+    _dpfa_vec(noise, torch.float32, P, "dpfa_clip_sum", "noise")
+    flags = (DPFA_ROWS_ARE_DELTAS if rows_are_deltas or global_ is None else 0) \
+        | (0 if add_global else DPFA_NO_GLOBAL_ADD)
+    call("fh_dpfa_clip_sum", ptr(rows), rows.stride(0), ptr(row_index), ptr(scale), C, P,
+         ptr(global_), ptr(out), ptr(sigma), ptr(noise), int(seed) & 0xFFFFFFFFFFFFFFFF,
+         int(stream_hi) & 0xFFFFFFFFFFFFFFFF, flags, stream_handle())
+    return out
+
+
 def pairwise_sqdist(rows, row_index=None, P=None):
     """[C, C] float64: dist[a][b] = sum_j ((double)(x_a[j] - x_b[j]))^2 over the rows selected
     by row_index (default: all), symmetric with a zero diagonal; same bits on every run."""

@@ -35,6 +35,19 @@ aggregate, so the ranks stay bit-identical without a broadcast.  A ``server_opt`
 is a robust rule uses that rule as ``aggregator``; given together with ``aggregator=`` it is
 refused.  The BN running statistics keep the plain FedAvg.  With ``server_opt=None`` nothing
 changes.
+
+``central_dp`` (a src.aggregation.dpfedavg.CentralDPConfig) replaces the FedAvg of the PARAMETER
+rows by the central DP-FedAvg aggregate: every client's delta clipped to the (adaptive) clip
+norm, averaged with uniform weights 1/m over ALL clients of the round and one Gaussian draw
+added to the average (src/aggregation/dpfedavg.py).  One rank, and ``exact=True`` on several
+(the all-gathered rows in global client order): the fused path.  Several ranks otherwise: each
+rank's clipped partial sum and clipped-bit count are all-reduced and every rank finishes with
+the same round key, so the ranks stay bit-identical without a per-round broadcast (the ranks
+adopt rank 0's ``dp_seed`` once, at construction: the one shared draw needs one secret).  The aggregate lands
+where FedAvg's would, so ``server_opt`` composes unchanged.  Refused together with ``dp`` (two
+mechanisms, no joint accounting) and with a robust ``aggregator`` (the sensitivity argument
+needs a sum).  The BN running statistics are outside the guarantee: ``release_buffers=False``
+leaves ``global_bufs`` as it was.  With ``central_dp=None`` nothing changes.
 """
 from __future__ import annotations
 
@@ -65,7 +78,8 @@ class RankRound:
     def __init__(self, template_model, all_train_sizes: Sequence[int], my_clients: Sequence[int],
                  epochs: int = 1, batch: int = 32, device="cuda", dp: Optional[DPConfig] = None,
                  group=None, lanes=None, compression=None, transform=None, dp_seed=None,
-                 shuffle_seed=None, exact=False, aggregator=None, server_opt=None):
+                 shuffle_seed=None, exact=False, aggregator=None, server_opt=None,
+                 central_dp=None):
         self.device = torch.device(device)
         self._template = template_model
         self.B, self.epochs, self.dp, self.group = batch, epochs, dp, group
@@ -87,6 +101,20 @@ class RankRound:
                 and dist.get_world_size(group) > 1:
             raise ops.FedHipError("a robust aggregator over several ranks needs exact=True: "
                                   "the rule is not a sum and cannot be all-reduced")
+        self.central = None
+        if central_dp is not None:
+            if dp is not None:
+                raise ops.FedHipError("central_dp and dp are two DP mechanisms with no joint "
+                                      "accounting: pass one")
+            if aggregator is not None:
+                raise ops.FedHipError("central_dp needs a sum (its sensitivity argument does): "
+                                      "a robust aggregator cannot be combined with it")
+            if not self.clients:
+                raise ops.FedHipError("central_dp: this rank holds no client")
+            try:  # 2 * bit_noise <= noise_multiplier is refused here, not in round one
+                central_dp.resolve(len(self.all_sizes))
+            except ValueError as e:
+                raise ops.FedHipError(f"central_dp: {e}") from e
         self.trainer = LanedTrainer(template_model, steps or [0], batch=batch, device=self.device,
                                     lanes=lanes, salt=self.rank)
         if self.slots:  # dropout / augmentation keyed by global client id (not rank / lane)
@@ -123,6 +151,21 @@ class RankRound:
         # id) — independent of the rank / lane / slot it lands on
         self.shuffle_seed = secrets.randbits(62) if shuffle_seed is None else int(shuffle_seed)
         self.partial = torch.zeros(self.P, device=self.device)
+        # central DP-FedAvg: its own draws come from the same round key as the update-level
+        # DP's, under stream words no client id can equal.  central_noise (fp32 [P]) replaces
+        # the draw (exact replay)
+        self.central_noise = None
+        if central_dp is not None:
+            from src.aggregation.dpfedavg import DPFedAvg
+            if self.distributed and dist.get_world_size(group) > 1:
+                # the aggregate carries ONE draw that every rank must make alike: the ranks
+                # agree on rank 0's secret once, here (no per-round broadcast).  The per-client
+                # streams of dp= tolerate per-rank secrets; this one does not.
+                box = [self.dp_seed]
+                src = 0 if group is None else dist.get_global_rank(group, 0)
+                dist.broadcast_object_list(box, src=src, group=group)
+                self.dp_seed = int(box[0])
+            self.central = DPFedAvg(central_dp, self.device, dp_seed=self.dp_seed)
         # global BN running statistics for evaluation (f-1; divergence D13): FedAvg of the
         # clients' buffers with the same weights.  Clients keep their own buffers (D4).
         self.Q = L.Q
@@ -178,18 +221,20 @@ class RankRound:
 
     def _exact_gather(self, rows, n):
         """[world * maxS, n]: this rank's rows (client-list order, zero padded) all-gathered;
-        global client k sits at row _x_rows[k]."""
+        global client k sits at row _x_rows[k].  The row stride is n rounded up to 4 floats, so
+        every row starts on a 16-byte boundary and the kernels take their vector paths."""
         world, maxS = self._x_world, self._x_maxS
         buf = self._x_buf.get(n)
         if buf is None:
-            buf = self._x_buf[n] = (torch.zeros(maxS, n, device=self.device),
-                                    torch.empty(world, maxS, n, device=self.device))
+            npad = (n + 3) // 4 * 4
+            buf = self._x_buf[n] = (torch.zeros(maxS, npad, device=self.device),
+                                    torch.empty(world, maxS, npad, device=self.device))
         send, recv = buf
         S = len(self.clients)
         if S:
-            torch.index_select(rows[:, :n], 0, self._x_mine, out=send[:S])
+            send[:S, :n].copy_(rows[:, :n].index_select(0, self._x_mine))
         dist.all_gather(list(recv.unbind(0)), send, group=self.group)
-        return recv.view(world * maxS, n)
+        return recv.view(world * maxS, -1)[:, :n]
 
     def _exact_fedavg(self, rows, n, out):
         """out = sum over ALL clients, in global client order, of fl32(w_k) * row_k: the
@@ -237,8 +282,15 @@ class RankRound:
         sopt = self.server_opt
         # with a server optimizer the aggregate lands in `partial` and the global steps to it
         agg_out = self.global_flat if sopt is None else self.partial
+        cdp = self.central
+        m_all = len(self.all_sizes)
+        keep_bufs = cdp is not None and not cdp.config.release_buffers
         if self.exact:  # bit-exact multi-rank FedAvg: all-gather + one sequential sum
-            if self.aggregator is None:
+            if cdp is not None:  # the fused path over every client's row, global client order
+                cdp.step_rows(self._exact_gather(tr.params, self.P), self.global_flat,
+                              self._x_idx, m_all, self._round_key(seed), out=agg_out,
+                              noise=self.central_noise)
+            elif self.aggregator is None:
                 self._exact_fedavg(tr.params, self.P, agg_out)
             else:  # the rule over every client's row, in global client order, on every rank
                 self.aggregator.aggregate_packed(self._exact_gather(tr.params, self.P),
@@ -246,13 +298,27 @@ class RankRound:
                                                  out=agg_out)
             if sopt is not None:
                 sopt.step_vector(self.partial, self.global_flat)
-            if self.Q:
+            if self.Q and not keep_bufs:
                 self._exact_fedavg(tr.bufs, self.Q, self.global_bufs)
             self.round_index += 1
             self._host_timing(_t)
             return metrics
         # FedAvg: this rank's partial sum in client-list order, then RCCL all-reduce.
-        if self.aggregator is None:
+        if cdp is not None:
+            key = self._round_key(seed)
+            if not distributed:
+                cdp.step_rows(tr.params, self.global_flat, self.rows, m_all, key, out=agg_out,
+                              noise=self.central_noise)
+            else:  # clipped partial sum and bit count, all-reduced; every rank finishes alike
+                part, bit_sum = cdp.partial_rows(tr.params, self.global_flat, self.rows, m_all,
+                                                 out=self.partial)
+                dist.all_reduce(part, op=dist.ReduceOp.SUM, group=self.group)
+                dist.all_reduce(bit_sum, op=dist.ReduceOp.SUM, group=self.group)
+                cdp.finish(part, bit_sum, self.global_flat, m_all, key, out=agg_out,
+                           noise=self.central_noise)
+            if sopt is not None:
+                sopt.step_vector(self.partial, self.global_flat)
+        elif self.aggregator is None:
             if sopt is not None and not distributed:  # weighted sum + step, one launch
                 sopt.step_rows(tr.params, self.w32, self.global_flat, self.rows)
             else:
@@ -269,7 +335,7 @@ class RankRound:
                                              row_index=self._agg_rows, out=agg_out)
             if sopt is not None:
                 sopt.step_vector(self.partial, self.global_flat)
-        if self.Q:
+        if self.Q and not keep_bufs:
             ops.fedavg_weighted_sum(tr.bufs, self.w32, self.global_bufs, row_index=self.rows,
                                     P=self.Q)
             if distributed:
@@ -294,6 +360,11 @@ class RankRound:
         return self._evaluator.evaluate(self.global_flat, self.global_bufs, data, labels,
                                         transform=self.transform)
 
+    def _round_key(self, seed):
+        """The round's Philox key, from the (secret by default) dp_seed."""
+        return (self.dp_seed * 6364136223846793005 + seed * 1442695040888963407
+                + self.round_index) & ((1 << 64) - 1)
+
     def _apply_dp(self, S, seed):
         """federated_trainer.py:434-462 for every client at once (budget bookkeeping is the
         caller's: privacy.py's tracker is host state)."""
@@ -302,8 +373,7 @@ class RankRound:
                                  tr.seg_offsets, S)
         total, coef, clipped, sigma = ops.dp_clip_coef(sq, dp.max_grad_norm, dp.epsilon, dp.delta)
         g = self.global_flat.view(1, -1).expand(S, -1)
-        key = (self.dp_seed * 6364136223846793005 + seed * 1442695040888963407
-               + self.round_index) & ((1 << 64) - 1)
+        key = self._round_key(seed)
         ops.dp_apply(tr.params, g, tr.params, coef, clipped, sigma, P=self.P, seed=key,
                      row_ids=self.slot_ids[:S], noise=self.dp_noise)
         self.last_dp = (total, clipped, sigma)

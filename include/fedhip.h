@@ -174,6 +174,89 @@ int fh_server_opt_step(const float* rows, int64_t row_stride, const int32_t* row
                        float* global, float* m, float* v, int32_t rule,
                        float server_lr, float beta1, float beta2, float tau, void* stream);
 
+/* ---------------- central DP-FedAvg (no reference counterpart) -------------
+ * McMahan et al., "Learning Differentially Private Recurrent Language Models" (ICLR 2018): the
+ * server clips every client's delta to an L2 norm C_t, averages the clipped deltas with uniform
+ * weights 1/m and adds ONE Gaussian draw of standard deviation z*C_t/m; the clip norm follows
+ * the target quantile of the clients' norms (Andrew et al., "Differentially Private Learning
+ * with Adaptive Clipping", NeurIPS 2021, Alg. 1, geometric update).  DESIGN.md §5 has the
+ * definition; x_k = rows[idx[k]*row_stride + .], row_index NULL = identity, g = global.
+ *
+ * The clip state lives on the device in `state`, FH_DPFA_STATE_DOUBLES doubles:
+ *   [FH_DPFA_CLIP]   C_t, the clip norm the next round uses (the caller initialises it)
+ *   [FH_DPFA_SIGMA]  sigma_avg of the last fh_dpfa_clip_coef, the fp32 value as a double
+ *   [FH_DPFA_BITSUM] this rank's sum of b_k of the last fh_dpfa_clip_coef
+ *   [FH_DPFA_BBAR]   bbar of the last fh_dpfa_clip_update
+ *   [FH_DPFA_NEXT]   C_{t+1} of the last update (what [FH_DPFA_CLIP] now holds)
+ *   [FH_DPFA_PREV]   C_t of the last update (what the last round clipped to)
+ * Nothing here allocates or synchronises with the host. */
+#define FH_DPFA_STATE_DOUBLES 8
+#define FH_DPFA_CLIP   0
+#define FH_DPFA_SIGMA  1
+#define FH_DPFA_BITSUM 2
+#define FH_DPFA_BBAR   3
+#define FH_DPFA_NEXT   4
+#define FH_DPFA_PREV   5
+/* Philox stream words (ctr_hi) of the server's draws: no client id (int64 >= 0) equals them. */
+#define FH_DPFA_STREAM_NOISE 0xFFFFFFFFFFFFFFFFull
+#define FH_DPFA_STREAM_BIT   0xFFFFFFFFFFFFFFFEull
+#define FH_DPFA_ROWS_ARE_DELTAS 1   /* d_k = x_k (global, if given, is only added back) */
+#define FH_DPFA_NO_GLOBAL_ADD   2   /* out = the clipped sum [+ noise], without g */
+
+/* sqnorm[k] = sum_j (double)d_kj^2 over the whole row, d_kj = fl32(x_kj - g_j) (global NULL:
+ * d = x).  The difference is fp32, squares and sums are fp64.  The summation order is a
+ * function of P and of the row's and g's offsets from a 16-byte boundary only: the same input
+ * gives the same bits on every run (no atomics).  A (clients, chunks) grid writes fp64 partials
+ * to `workspace` (fh_dpfa_row_sqnorm_workspace bytes), a second small launch adds them in
+ * order.  16-byte loads where the row and g share their offset from a 16-byte boundary.
+ * FH_E_INVALID for num_clients < 1, P < 0, null rows (P > 0) / sqnorm, a short workspace.
+ * P == 0 stores zeros. */
+size_t fh_dpfa_row_sqnorm_workspace(int32_t num_clients, int64_t P);
+int fh_dpfa_row_sqnorm(const float* rows, int64_t row_stride, const int32_t* row_index,
+                       const float* global, int32_t num_clients, int64_t P, void* workspace,
+                       size_t workspace_bytes, double* sqnorm, void* stream);
+
+/* With C_t = state[FH_DPFA_CLIP], n_k = sqrt(sqnorm[k]) and m = total_clients (the round's
+ * clients on ALL ranks; num_clients are this rank's):
+ *     bits[k]  = n_k <= C_t
+ *     c_k      = n_k > C_t ? fl32(C_t / n_k) : 1.0f       fp64 division; n_k = 0 or NaN: 1
+ *     scale[k] = fl32(c_k * fl32(1/m))                    one fp32 multiply
+ *     sigma[0] = fl32(z_delta * C_t / m)                  fp64, left to right; sigma may be NULL
+ * and state[FH_DPFA_SIGMA], state[FH_DPFA_BITSUM] = sum_k bits[k].  FH_E_INVALID for
+ * num_clients < 1, total_clients < num_clients, a negative or non-finite z_delta, null
+ * pointers. */
+int fh_dpfa_clip_coef(const double* sqnorm, int32_t num_clients, int32_t total_clients,
+                      double z_delta, double* state, float* scale, int32_t* bits, float* sigma,
+                      void* stream);
+
+/* bbar = (bit_sum[0] + bit_noise * xi) / m;  C_{t+1} = C_t * exp(-clip_lr * (bbar - quantile))
+ * in fp64, xi = lane 0 of the fp32 Box-Muller on Philox(seed, FH_DPFA_STREAM_BIT, 0).  With
+ * clip_lr == 0: no draw, bbar = bit_sum[0] / m, C_{t+1} = C_t.  bit_sum is a device double
+ * (&state[FH_DPFA_BITSUM] on one rank, its all-reduce on several).  Stores BBAR, NEXT, PREV and
+ * CLIP = C_{t+1}.  FH_E_INVALID for total_clients < 1, a quantile outside [0, 1], a negative
+ * or non-finite clip_lr / bit_noise, null pointers. */
+int fh_dpfa_clip_update(double* state, const double* bit_sum, int32_t total_clients,
+                        double target_quantile, double clip_lr, double bit_noise, uint64_t seed,
+                        void* stream);
+
+/* Per coordinate j, every operation one rounded fp32 operation, never fused:
+ *     d_k  = fl32(x_k[j] - g[j])       FH_DPFA_ROWS_ARE_DELTAS or global NULL: d_k = x_k[j]
+ *     acc  = (((0 + scale[0]*d_0) + scale[1]*d_1) + ...)              rows in index order
+ *     nu   = noise_in ? noise_in[j] : fl32(sigma[0] * G_j)
+ *            G_j = lane j%4 of the fp32 Box-Muller on Philox(seed, stream_hi, j/4), as fh_dp_apply's
+ *     t    = (noise_in || sigma) ? acc + nu : acc                     no noise: no add
+ *     out  = global && !FH_DPFA_NO_GLOBAL_ADD ? g[j] + t : t
+ * any NaN is stored as the one quiet NaN 0x7FC00000.  out may alias global or the rows.  With
+ * FH_DPFA_ROWS_ARE_DELTAS, one row and scale = {1} on an all-reduced partial the kernel only
+ * adds the noise and g.  FH_E_INVALID for num_clients < 1, P < 0, unknown flags, global NULL
+ * without FH_DPFA_ROWS_ARE_DELTAS, null rows / scale / out.  P == 0 is a no-op.  16-byte loads
+ * and stores when row_stride % 4 == 0 and rows, global, out and noise_in are 16-byte aligned;
+ * a scalar kernel with the same bits covers everything else.  Reads (C+1)*P floats, writes P. */
+int fh_dpfa_clip_sum(const float* rows, int64_t row_stride, const int32_t* row_index,
+                     const float* scale, int32_t num_clients, int64_t P, const float* global,
+                     float* out, const float* sigma, const float* noise_in, uint64_t seed,
+                     uint64_t stream_hi, int32_t flags, void* stream);
+
 /* ---------------- update-level DP (privacy.py:107-144, 183-254) ----------
  * delta = fl32(local - global) (global may be NULL: delta = local).
  * seg_sqnorm[z*nseg+t] = sum over segment t of delta^2, accumulated in fp64. */
