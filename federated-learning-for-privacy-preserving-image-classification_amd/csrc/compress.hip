@@ -18,7 +18,9 @@
 // zero point are recomputed from the chunk partials in the reference's double arithmetic
 // (scale = 2*max|v| / (L-1) or (max-min)/(L-1), zp = (L-1)//2 or -round(min/scale)) and
 // codes = clamp(rint(v / fl32(scale) + zp), 0, L-1), dense = (code - zp) * fl32(scale),
-// all fp32 like ATen's CPU kernels.  Bit-exact with the reference (golden G8).
+// all fp32 like ATen's CPU kernels (16 bits: the code wraps through int16 first, as the
+// reference's int16 code tensor does).  Bit-exact with the reference (golden G8,
+// tests/golden/compress_edges.json).
 //
 // Top-k by |v| (10 launches + a memset): MSB-first radix select over the 31-bit magnitude keys —
 // four 8-bit histogram passes (LDS histograms, integer atomics: deterministic) each
@@ -140,6 +142,9 @@ quant_apply_kernel(const float* x, int64_t x_cs, const float* __restrict__ base,
         if (q != q) q = 0.f;                        // ... and converts to code 0 on x86
         if (crow) crow[i] = (uint8_t)(int)q;
         if (orow) {
+            // 16 bits: the reference holds codes 0..65535 in int16, so codes >= 32768 wrap
+            // to negative and are dequantised from the wrapped value
+            if (levels > 32768) q = (float)(int16_t)(int)q;
             const float d = bad ? v : (q - fzp) * fs;
             orow[i] = br ? br[i] + d : d;
         }

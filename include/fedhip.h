@@ -1006,6 +1006,8 @@ int fh_gather_u8(const uint8_t* data, const int64_t* labels, const int64_t* idx,
  *                    per-segment scale (double) and zero point.  Asymmetric mode on a
  *                    constant segment raises in the reference (round(inf)); here that
  *                    segment passes through unchanged and zp_out = INT64_MIN.
+ *                    bits = 16: as in the reference, codes >= 32768 wrap through int16
+ *                    before they are dequantised.
  * fh_topk_rows       TopKSparsificationCompressor._sparsify_tensor + _desparsify_tensor
  *                    (:327-365) with k = seg_k[s] (device int64[nseg]); keep (nullable)
  *                    gets the uint8 keep-mask.  Ties at the k-th magnitude: lowest

@@ -43,7 +43,9 @@ def quantize(x: np.ndarray, bits: int = 8, symmetric: bool = True):
     q = np.clip(q, 0, levels - 1)
     q = np.nan_to_num(q, nan=0.0)  # scale 0: x86 converts the NaN codes to 0
     dt = np.uint8 if bits <= 8 else (np.int16 if bits <= 16 else np.int32)
-    return q.astype(dt), scale, zp
+    # bits == 16: the reference stores codes 0..65535 as int16, so codes >= 32768 wrap to
+    # negative (x86 float -> int32 -> low 16 bits) and dequantise from the wrapped value
+    return q.astype(np.int64).astype(dt), scale, zp
 
 
 def dequantize(codes: np.ndarray, scale: float, zero_point: int) -> np.ndarray:
