@@ -193,6 +193,12 @@ SIGNATURES = {
                                P, SZ, P]),
     "fh_topk_workspace": (I64, [I32, I32, I32]),
     "fh_topk_rows": (I32, [P, I64, P, I64, P, I64, P, I64, I32, P, P, P, I32, I32, P, SZ, P]),
+    "fh_ef_fold": (I32, [P, I64, P, I64, P, I64, I32, P, P, I32, I32, P]),
+    "fh_ef_topk_finish": (I32, [P, I64, P, I64, P, I64, P, I64, I32, P, P, I32, I32, P]),
+    "fh_ef_quant_finish": (I32, [P, I64, P, I64, P, I64, P, I64, I32, P, P, I32, I32, P]),
+    "fh_squant_workspace": (I64, [I32, I32]),
+    "fh_squant_rows": (I32, [P, I64, P, I64, P, I64, P, I64, P, I64, P, I64, I32, P, P, I32, I32,
+                             I32, I32, U64, P, P, I64, P, P, P, SZ, P]),
     "fh_eval_metrics": (I32, [P, I64, P, I64, P, I32, I32, I32, P, P, P, P, P]),
     "fh_avgpool_fwd": (I32, [P, I64, P, I64, P, I32, I32, I32, I32, P]),
     "fh_avgpool_bwd": (I32, [P, I64, P, I64, P, I32, I32, I32, I32, P]),

@@ -11,6 +11,11 @@ before FedAvg:
 which is what a server would reconstruct from a compressed upload of the delta.
 ``RankRound(compression=...)`` applies it to every client row of a round in
 one pass per kernel (no host sync).
+
+Not in the reference (csrc/efcomp.hip), off by default: error feedback
+(``CompressionConfig(error_feedback=True)``: the client keeps what compression removed and
+sends it with a later update) and unbiased stochastic rounding for the quantiser
+(``stochastic=True``).
 """
 from __future__ import annotations
 
@@ -25,15 +30,27 @@ from .ops import _ws
 
 @dataclass
 class CompressionConfig:
-    """algorithm: "quantization" (bits, symmetric) or "topk" (sparsity_ratio)."""
+    """algorithm: "quantization" (bits, symmetric) or "topk" (sparsity_ratio).
+
+    error_feedback: every client keeps what compression removed from its update and adds it
+    to its next one (needs per-client residual rows).  stochastic
+    ("quantization" only, bits >= 2): unbiased stochastic rounding instead of the reference's
+    round-half-to-even.  Both are off by default: the reference's compressors, bit for bit."""
     algorithm: str = "topk"
     sparsity_ratio: float = 0.9
     bits: int = 8
     symmetric: bool = True
+    error_feedback: bool = False
+    stochastic: bool = False
 
     def __post_init__(self):
         if self.algorithm not in ("quantization", "topk"):
             raise FedHipError(f"unknown compression algorithm {self.algorithm!r}")
+        if self.stochastic and self.algorithm != "quantization":
+            raise FedHipError("stochastic rounding is an option of algorithm='quantization' "
+                              f"(got {self.algorithm!r})")
+        if self.stochastic and not 2 <= self.bits <= 16:
+            raise FedHipError(f"stochastic quantisation needs bits in [2, 16] (got {self.bits})")
 
 
 def topk_k(numel: int, sparsity_ratio: float) -> int:
@@ -52,6 +69,7 @@ class SegmentPlan:
         self.device = torch.device(device)
         self.chunk = int(lib.fh_compress_chunk_elems())
         offs = [int(o) for o in seg_offsets]
+        self.end = offs[-1]  # one past the last element of a row the plan covers
         self.lengths = [b - a for a, b in zip(offs[:-1], offs[1:])]
         if not self.lengths or min(self.lengths) <= 0:
             raise FedHipError("compression needs non-empty segments")
@@ -100,9 +118,104 @@ def topk_rows(plan: SegmentPlan, x, nclients, sparsity_ratio=0.9, base=None, out
     return out
 
 
+# ------------------------------------------------------------------ error feedback, stochastic
+def _plan_args(plan: SegmentPlan):
+    return ptr(plan.seg_offsets), ptr(plan.chunk_offsets), plan.nseg, plan.nchunks
+
+
+def ef_fold(plan: SegmentPlan, x, resid, nclients, base=None):
+    """resid <- (x - base) + resid, the compensated update v (fh_ef_fold)."""
+    call("fh_ef_fold", ptr(x), x.stride(0), ptr(base), _cs(base), ptr(resid), resid.stride(0),
+         nclients, *_plan_args(plan), stream_handle())
+    return resid
+
+
+def ef_topk_finish(plan: SegmentPlan, keep, resid, x_out, nclients, base=None):
+    """With keep = the top-k mask of v = resid: x_out <- base + (keep ? v : 0), resid <- keep ?
+    0 : v (fh_ef_topk_finish)."""
+    call("fh_ef_topk_finish", ptr(base), _cs(base), ptr(keep), keep.stride(0), ptr(resid),
+         resid.stride(0), ptr(x_out), x_out.stride(0), nclients, *_plan_args(plan),
+         stream_handle())
+    return x_out
+
+
+def ef_quant_finish(plan: SegmentPlan, c, resid, x_out, nclients, base=None):
+    """With c = dequantize(quantize(v)), v = resid: x_out <- base + c, resid <- v - c
+    (fh_ef_quant_finish); x_out may be c."""
+    call("fh_ef_quant_finish", ptr(base), _cs(base), ptr(c), c.stride(0), ptr(resid),
+         resid.stride(0), ptr(x_out), x_out.stride(0), nclients, *_plan_args(plan),
+         stream_handle())
+    return x_out
+
+
+def squant_rows(plan: SegmentPlan, x, nclients, bits, symmetric, key, row_ids, base=None,
+                resid=None, out=None, codes=None, resid_out=None, scale_out=None, lo_out=None,
+                words=None):
+    """Stochastic-rounding quantiser (fh_squant_rows): out = base + deq(v) with v = x - base, or
+    v = resid when given (the folded residual; x may then be None).  row_ids: int64 global
+    client ids; words (uint32 rows) replaces the Philox draw."""
+    lib = load()
+    dev = (resid if x is None else x).device
+    need = int(lib.fh_squant_workspace(nclients, plan.nchunks))
+    ws = _ws(dev).get(max(need, 1))
+    call("fh_squant_rows", ptr(x), _cs(x), ptr(base), _cs(base), ptr(resid), _cs(resid), ptr(out),
+         _cs(out), ptr(codes), _cs(codes), ptr(resid_out), _cs(resid_out), nclients,
+         *_plan_args(plan), int(bits), int(bool(symmetric)), int(key) & ((1 << 64) - 1),
+         ptr(row_ids), ptr(words), _cs(words), ptr(scale_out), ptr(lo_out), ptr(ws), ws.numel(),
+         stream_handle())
+    return out
+
+
+_KEEP: dict = {}
+
+
+def _keep_scratch(like, nclients):
+    """uint8 keep mask [nclients, row stride of `like`] for the error-feedback top-k, one per
+    (device, stream), grow-only."""
+    k = (str(like.device), torch.cuda.current_stream(like.device).cuda_stream)
+    n, w = nclients, like.stride(0)
+    t = _KEEP.get(k)
+    if t is None or t.shape[0] < n or t.shape[1] < w:
+        t = _KEEP[k] = torch.empty(n, w, dtype=torch.uint8, device=like.device)
+    return t
+
+
 def compress_rows(plan: SegmentPlan, cfg: CompressionConfig, rows, nclients,
-                  base: Optional[torch.Tensor] = None):
-    """In place: rows[:nclients] <- base + decompress(compress(rows - base))."""
+                  base: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
+                  key: Optional[int] = None, row_ids: Optional[torch.Tensor] = None,
+                  words: Optional[torch.Tensor] = None):
+    """In place: rows[:nclients] <- base + decompress(compress(rows - base)).
+
+    cfg.error_feedback: the update compressed is v = (rows - base) + resid and resid
+    ([>= nclients, >= P] fp32, updated in place) keeps v - decompress(compress(v)).
+    cfg.stochastic: key (the round's Philox key) and row_ids (int64 global client ids) select
+    the random words; words (uint32 rows) replaces them."""
+    if cfg.error_feedback:
+        if resid is None:
+            raise FedHipError("compression with error_feedback needs the residual rows (resid=)")
+        if resid.dtype != torch.float32 or resid.dim() != 2 or resid.shape[0] < nclients \
+                or resid.shape[1] < plan.end or resid.stride(1) != 1:
+            raise FedHipError("compression: resid must be fp32 [>= nclients, >= P] rows")
+    if cfg.stochastic and (key is None or row_ids is None):
+        raise FedHipError("stochastic compression needs key= and row_ids=")
+    if cfg.stochastic:
+        if not cfg.error_feedback:
+            return squant_rows(plan, rows, nclients, cfg.bits, cfg.symmetric, key, row_ids,
+                               base=base, out=rows, words=words)
+        ef_fold(plan, rows, resid, nclients, base=base)
+        return squant_rows(plan, None, nclients, cfg.bits, cfg.symmetric, key, row_ids, base=base,
+                           resid=resid, out=rows, resid_out=resid, words=words)
+    if not cfg.error_feedback:
+        if cfg.algorithm == "topk":
+            return topk_rows(plan, rows, nclients, cfg.sparsity_ratio, base=base, out=rows)
+        return quantize_rows(plan, rows, nclients, cfg.bits, cfg.symmetric, base=base, out=rows)
+    ef_fold(plan, rows, resid, nclients, base=base)
     if cfg.algorithm == "topk":
-        return topk_rows(plan, rows, nclients, cfg.sparsity_ratio, base=base, out=rows)
-    return quantize_rows(plan, rows, nclients, cfg.bits, cfg.symmetric, base=base, out=rows)
+        keep = _keep_scratch(rows, nclients)
+        topk_rows(plan, resid, nclients, cfg.sparsity_ratio, keep=keep)
+        return ef_topk_finish(plan, keep, resid, rows, nclients, base=base)
+    # the rows are rewritten by the finish anyway: they hold c in between
+    quantize_rows(plan, resid, nclients, cfg.bits, cfg.symmetric, out=rows)
+    return ef_quant_finish(plan, rows, resid, rows, nclients, base=base)
+
+

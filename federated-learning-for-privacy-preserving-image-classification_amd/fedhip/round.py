@@ -48,6 +48,20 @@ where FedAvg's would, so ``server_opt`` composes unchanged.  Refused together wi
 mechanisms, no joint accounting) and with a robust ``aggregator`` (the sensitivity argument
 needs a sum).  The BN running statistics are outside the guarantee: ``release_buffers=False``
 leaves ``global_bufs`` as it was.  With ``central_dp=None`` nothing changes.
+
+``compression`` (a fedhip.compress.CompressionConfig) compresses every client's update delta
+before any aggregation sees the rows.  The order of a round is train -> ``dp`` -> compression ->
+aggregation.  ``error_feedback=True`` makes the round own ``residual`` ([S, P], one row per slot,
+zero at construction, kept across ``run()`` calls, cleared by ``reset_compression_state()``):
+each client compresses its delta plus its residual and keeps what was not sent.  With ``dp`` the
+residual therefore also carries what compression removed from the NOISED delta; compression and
+the residual are post-processing of the mechanism's output, so the DP statement is untouched.
+``stochastic=True`` draws the quantiser's rounding words from the round key under the clients'
+global ids (``squant_words``, uint32 [S, P], replaces the draw for exact replay).  Compression
+works on a rank's own rows, and the client-to-rank assignment is fixed for a RankRound, so it
+composes unchanged with ``exact``, ``aggregator``, ``server_opt``, ``central_dp`` and several
+ranks.  A client with an empty shard sends from its residual at FedAvg weight 0.  With the
+default CompressionConfig options nothing changes.
 """
 from __future__ import annotations
 
@@ -184,9 +198,17 @@ class RankRound:
         # update compression before FedAvg (f-3; insertion point D14): delta vs the global
         self.compression = compression
         self._cplan = None
+        # error feedback: one residual row per slot, kept across run() calls; squant_words
+        # (uint32 [S, P]) replaces the stochastic quantiser's Philox words (exact replay)
+        self.residual = None
+        self.squant_words = None
         if compression is not None:
             from .compress import SegmentPlan
             self._cplan = SegmentPlan(L.seg_offsets(), self.device)
+            if compression.error_feedback:
+                # row stride padded to 64 floats: every row starts on a 16-byte boundary
+                self.residual = torch.zeros(max(len(self.slots), 1), (self.P + 63) // 64 * 64,
+                                            device=self.device)[:, :self.P]
         self.exact = bool(exact) and self.distributed
         if self.exact:
             self._init_exact()
@@ -251,6 +273,12 @@ class RankRound:
     def set_global(self, flat: torch.Tensor):
         self.global_flat.copy_(flat)
 
+    def reset_compression_state(self):
+        """Forget every client's error-feedback residual (a new training run, or a new
+        client-to-slot assignment, on the same RankRound)."""
+        if self.residual is not None:
+            self.residual.zero_()
+
     def run(self, data, labels, slot_offsets: Sequence[int], optimizer_type="sgd", lr=0.01,
             seed=0, generator=None, serialize_lanes=False):
         """One round. data/labels: this rank's train shards, slot k's at slot_offsets[k]."""
@@ -276,8 +304,14 @@ class RankRound:
             self._apply_dp(S, seed)
         if self.compression is not None:
             from .compress import compress_rows
+            extra = {}
+            if self.compression.error_feedback:
+                extra["resid"] = self.residual
+            if self.compression.stochastic:
+                extra.update(key=self._round_key(seed), row_ids=self.slot_ids[:S],
+                             words=self.squant_words)
             compress_rows(self._cplan, self.compression, tr.params, S,
-                          base=self.global_flat.view(1, -1).expand(S, -1))
+                          base=self.global_flat.view(1, -1).expand(S, -1), **extra)
         distributed = self.distributed
         sopt = self.server_opt
         # with a server optimizer the aggregate lands in `partial` and the global steps to it

@@ -34,6 +34,8 @@
  *   fh_eval_metrics          LocalTrainer.evaluate_model metrics (training.py:307-360)
  *   fh_quantize_rows         QuantizationCompressor (compression.py:123-247)
  *   fh_topk_rows             TopKSparsificationCompressor (compression.py:250-368)
+ *   fh_ef_fold / fh_ef_topk_finish / fh_ef_quant_finish / fh_squant_rows
+ *                            not in the reference (error feedback, stochastic rounding)
  */
 #ifndef FEDHIP_H_
 #define FEDHIP_H_
@@ -1024,6 +1026,73 @@ int fh_topk_rows(const float* x, int64_t x_cs, const float* base, int64_t base_c
                  int64_t out_cs, uint8_t* keep, int64_t keep_cs, int32_t nclients,
                  const int64_t* seg_offsets, const int32_t* chunk_offsets, const int64_t* seg_k,
                  int32_t nseg, int32_t nchunks, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------- error feedback and stochastic rounding (not in the reference) -----
+ * Same conventions as the block above: packed rows with element strides, base nullable
+ * (base_cs 0 broadcasts one row), segments by seg_offsets / chunk_offsets, nothing outside
+ * [seg_offsets[0], seg_offsets[nseg]) of a row is read or written, one launch per stage for all
+ * clients.  fl32() marks one rounded fp32 operation; none is ever fused with another.
+ *
+ * Error feedback (Stich et al. 2018; Karimireddy et al. 2019): resid[z] is client z's residual
+ * row, what compression has removed from its earlier updates.
+ *
+ * fh_ef_fold          resid[z][i] = fl32( fl32(x[z][i] - base[z][i]) + resid[z][i] )
+ *                     (base NULL: fl32(x + resid)).  The result is called v below.
+ * fh_ef_topk_finish   after fh_topk_rows(x = resid, base = NULL, out = NULL, keep) has written
+ *                     the uint8 keep mask of v:  d = keep ? v : +0.0,
+ *                     x_out = fl32(base + d) (base NULL: d),  resid = keep ? +0.0 : v.
+ *                     That is fh_topk_rows' own output for an update whose delta is v: a kept
+ *                     coordinate carries fl32(base + v), a dropped one base (a base of -0.0
+ *                     comes out +0.0, as there).  The tie rule is fh_topk_rows'.
+ * fh_ef_quant_finish  after fh_quantize_rows(x = resid, base = NULL, out = c) has written the
+ *                     dequantised v:  x_out = fl32(base + c) (base NULL: c),
+ *                     resid = fl32(v - c).  x_out may be c.
+ *
+ * fh_squant_rows      stochastic-rounding quantiser (QSGD, Alistarh et al. 2017), bits in
+ *                     [2, 16], per (client row, segment).  v = x - base (base NULL: x), or, when
+ *                     resid is given, v = resid (fh_ef_fold ran first; x is not read).
+ *   symmetric:   a = max|v|, qmax = 2^(bits-1) - 1, scale = fl32(a / qmax), t = fl32(v / scale),
+ *                q = clamp(floor(t) + up, -qmax, qmax), deq = fl32(q * scale)
+ *   asymmetric:  lo = min v, hi = max v, L = 2^bits - 1, scale = fl32(fl32(hi - lo) / L),
+ *                t = fl32(fl32(v - lo) / scale), q = clamp(floor(t) + up, 0, L),
+ *                deq = fl32(lo + fl32(q * scale))
+ *   up:          f = fl32(t - floor(t)) (exact except for a tiny negative t, where it rounds
+ *                to 1), thr = (uint32)(f * 2^24), up = (r >> 8) < thr — an integer compare, no
+ *                transcendental.  Divisions are IEEE round-to-nearest.
+ *   r:           the element's 32-bit random word.  For flat row index i it is word i & 3 of
+ *                Philox4x32-10(key, ctr_hi = ids[z] | FH_SQUANT_STREAM_BIT, ctr_lo = i >> 2),
+ *                ids: device int64[nclients], the global client ids (below 2^62).  The bit
+ *                keeps the stream apart from the update-level DP noise (ctr_hi = id under the
+ *                same round key) and from the FH_DPFA_STREAM_* words (bit 63 set).  words
+ *                (nullable, uint32 rows with stride words_cs, indexed like x) replaces the
+ *                draw: r = words[z][i] (exact replay).
+ *   scale == 0:  (all-zero segment, constant segment in asymmetric mode, one element) the
+ *                segment passes through: deq = v, codes 0.
+ *   outputs:     out = fl32(base + deq) (base NULL: deq; nullable; may alias x);
+ *                codes (nullable, bits <= 8): uint8 q + qmax (symmetric) or q (asymmetric);
+ *                scale_out / lo_out (nullable, fp32 [nclients][nseg]; lo_out = 0 in symmetric
+ *                mode); resid_out (nullable; may alias resid) = fl32(v - deq).
+ *   Non-finite inputs: unspecified.  ws: fh_squant_workspace(nclients, nchunks) bytes. */
+#define FH_SQUANT_STREAM_BIT (1ull << 62)
+int fh_ef_fold(const float* x, int64_t x_cs, const float* base, int64_t base_cs, float* resid,
+               int64_t resid_cs, int32_t nclients, const int64_t* seg_offsets,
+               const int32_t* chunk_offsets, int32_t nseg, int32_t nchunks, void* stream);
+int fh_ef_topk_finish(const float* base, int64_t base_cs, const uint8_t* keep, int64_t keep_cs,
+                      float* resid, int64_t resid_cs, float* x_out, int64_t x_out_cs,
+                      int32_t nclients, const int64_t* seg_offsets, const int32_t* chunk_offsets,
+                      int32_t nseg, int32_t nchunks, void* stream);
+int fh_ef_quant_finish(const float* base, int64_t base_cs, const float* c, int64_t c_cs,
+                       float* resid, int64_t resid_cs, float* x_out, int64_t x_out_cs,
+                       int32_t nclients, const int64_t* seg_offsets, const int32_t* chunk_offsets,
+                       int32_t nseg, int32_t nchunks, void* stream);
+int64_t fh_squant_workspace(int32_t nclients, int32_t nchunks);
+int fh_squant_rows(const float* x, int64_t x_cs, const float* base, int64_t base_cs,
+                   const float* resid, int64_t resid_cs, float* out, int64_t out_cs,
+                   uint8_t* codes, int64_t codes_cs, float* resid_out, int64_t resid_out_cs,
+                   int32_t nclients, const int64_t* seg_offsets, const int32_t* chunk_offsets,
+                   int32_t nseg, int32_t nchunks, int32_t bits, int32_t symmetric, uint64_t key,
+                   const int64_t* ids, const uint32_t* words, int64_t words_cs, float* scale_out,
+                   float* lo_out, void* ws, size_t ws_bytes, void* stream);
 
 /* ---------------- evaluation metrics (training.py:214-242, 307-360) ----------
  * Eval-mode metrics of [nclients][batch][K] logits: per image the first-index
