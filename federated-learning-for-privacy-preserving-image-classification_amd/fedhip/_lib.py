@@ -199,6 +199,12 @@ SIGNATURES = {
     "fh_squant_workspace": (I64, [I32, I32]),
     "fh_squant_rows": (I32, [P, I64, P, I64, P, I64, P, I64, P, I64, P, I64, I32, P, P, I32, I32,
                              I32, I32, U64, P, P, I64, P, P, P, SZ, P]),
+    "fh_topk_pack_workspace": (I64, [I32, I32]),
+    "fh_topk_pack_rows": (I32, [P, I64, P, I64, P, I64, P, I64, P, I64, P, I32, P, P, P, I32, I32,
+                                P, SZ, P]),
+    "fh_sparse_validate": (I32, [P, I64, I32, P, P, I32, P, P]),
+    "fh_sparse_unpack_rows": (I32, [P, I64, P, I64, P, I64, P, I64, I32, P, P, P, I32, I32, P]),
+    "fh_sparse_fedavg": (I32, [P, I64, P, I64, P, P, I32, P, P, P, P, I32, I32, P, I32, P]),
     "fh_eval_metrics": (I32, [P, I64, P, I64, P, I32, I32, I32, P, P, P, P, P]),
     "fh_avgpool_fwd": (I32, [P, I64, P, I64, P, I32, I32, I32, I32, P]),
     "fh_avgpool_bwd": (I32, [P, I64, P, I64, P, I32, I32, I32, I32, P]),

@@ -35,13 +35,17 @@ class CompressionConfig:
     error_feedback: every client keeps what compression removed from its update and adds it
     to its next one (needs per-client residual rows).  stochastic
     ("quantization" only, bits >= 2): unbiased stochastic rounding instead of the reference's
-    round-half-to-even.  Both are off by default: the reference's compressors, bit for bit."""
+    round-half-to-even.  sparse ("topk" only): a round also keeps every client's update as
+    the packed (index, value) payload of fedhip/sparse.py and aggregates from it where it can
+    (DESIGN.md D21); the global model is the same, bit for bit.  All are off by default: the
+    reference's compressors, bit for bit."""
     algorithm: str = "topk"
     sparsity_ratio: float = 0.9
     bits: int = 8
     symmetric: bool = True
     error_feedback: bool = False
     stochastic: bool = False
+    sparse: bool = False
 
     def __post_init__(self):
         if self.algorithm not in ("quantization", "topk"):
@@ -51,6 +55,9 @@ class CompressionConfig:
                               f"(got {self.algorithm!r})")
         if self.stochastic and not 2 <= self.bits <= 16:
             raise FedHipError(f"stochastic quantisation needs bits in [2, 16] (got {self.bits})")
+        if self.sparse and self.algorithm != "topk":
+            raise FedHipError("sparse payloads are an option of algorithm='topk' "
+                              f"(got {self.algorithm!r})")
 
 
 def topk_k(numel: int, sparsity_ratio: float) -> int:
@@ -183,13 +190,24 @@ def _keep_scratch(like, nclients):
 def compress_rows(plan: SegmentPlan, cfg: CompressionConfig, rows, nclients,
                   base: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
                   key: Optional[int] = None, row_ids: Optional[torch.Tensor] = None,
-                  words: Optional[torch.Tensor] = None):
+                  words: Optional[torch.Tensor] = None, sparse_out=None,
+                  rewrite_rows: bool = True):
     """In place: rows[:nclients] <- base + decompress(compress(rows - base)).
 
     cfg.error_feedback: the update compressed is v = (rows - base) + resid and resid
     ([>= nclients, >= P] fp32, updated in place) keeps v - decompress(compress(v)).
     cfg.stochastic: key (the round's Philox key) and row_ids (int64 global client ids) select
-    the random words; words (uint32 rows) replaces them."""
+    the random words; words (uint32 rows) replaces them.
+    sparse_out (a fedhip.sparse.SparseUpdates of this plan at cfg.sparsity_ratio, "topk" only)
+    also receives the kept (index, value) pairs of every client.  rewrite_rows=False (with
+    sparse_out, without error feedback) then leaves rows as they came: the payload is the
+    update."""
+    if sparse_out is not None:
+        if cfg.algorithm != "topk" or cfg.stochastic:
+            raise FedHipError("sparse_out= needs algorithm='topk'")
+        if sparse_out.plan.plan is not plan or sparse_out.plan.ratio != float(cfg.sparsity_ratio):
+            raise FedHipError("sparse_out= was laid out for another segment plan or ratio")
+        from .sparse import sparse_unpack_rows, topk_pack_rows
     if cfg.error_feedback:
         if resid is None:
             raise FedHipError("compression with error_feedback needs the residual rows (resid=)")
@@ -206,6 +224,13 @@ def compress_rows(plan: SegmentPlan, cfg: CompressionConfig, rows, nclients,
         return squant_rows(plan, None, nclients, cfg.bits, cfg.symmetric, key, row_ids, base=base,
                            resid=resid, out=rows, resid_out=resid, words=words)
     if not cfg.error_feedback:
+        if sparse_out is not None:
+            keep = _keep_scratch(rows, nclients)
+            topk_rows(plan, rows, nclients, cfg.sparsity_ratio, base=base, keep=keep)
+            topk_pack_rows(sparse_out, rows, keep, nclients, base=base)
+            if rewrite_rows:
+                sparse_unpack_rows(sparse_out, rows, nclients, base=base)
+            return rows
         if cfg.algorithm == "topk":
             return topk_rows(plan, rows, nclients, cfg.sparsity_ratio, base=base, out=rows)
         return quantize_rows(plan, rows, nclients, cfg.bits, cfg.symmetric, base=base, out=rows)
@@ -213,9 +238,9 @@ def compress_rows(plan: SegmentPlan, cfg: CompressionConfig, rows, nclients,
     if cfg.algorithm == "topk":
         keep = _keep_scratch(rows, nclients)
         topk_rows(plan, resid, nclients, cfg.sparsity_ratio, keep=keep)
+        if sparse_out is not None:  # before the finish: it clears the kept v from resid
+            topk_pack_rows(sparse_out, resid, keep, nclients)
         return ef_topk_finish(plan, keep, resid, rows, nclients, base=base)
     # the rows are rewritten by the finish anyway: they hold c in between
     quantize_rows(plan, resid, nclients, cfg.bits, cfg.symmetric, out=rows)
     return ef_quant_finish(plan, rows, resid, rows, nclients, base=base)
-
-

@@ -62,6 +62,14 @@ works on a rank's own rows, and the client-to-rank assignment is fixed for a Ran
 composes unchanged with ``exact``, ``aggregator``, ``server_opt``, ``central_dp`` and several
 ranks.  A client with an empty shard sends from its residual at FedAvg weight 0.  With the
 default CompressionConfig options nothing changes.
+
+``sparse=True`` (top-k only; fedhip/sparse.py) also packs every client's kept
+coordinates into (index, value) payload rows, kept as ``last_sparse`` (one row per slot, rewritten
+by every ``run()``; ``wire.sparse_to_payloads`` turns it into the reference's upload dicts).  The
+plain FedAvg routes (no ``aggregator``, no ``central_dp``, not ``exact``) sum from the payload and
+leave the trained rows as they are; with ``server_opt`` on one rank the sum lands in ``partial``
+and ``step_vector`` follows.  The other routes rebuild the dense rows from the payload first.
+The global model, ``global_bufs`` and ``residual`` are bit for bit those of ``sparse=False``.
 """
 from __future__ import annotations
 
@@ -209,6 +217,14 @@ class RankRound:
                 # row stride padded to 64 floats: every row starts on a 16-byte boundary
                 self.residual = torch.zeros(max(len(self.slots), 1), (self.P + 63) // 64 * 64,
                                             device=self.device)[:, :self.P]
+        # sparse top-k (D21): the slots' (index, value) payload rows, rewritten every round;
+        # last_sparse is the payload of the last run()
+        self._sparse = None
+        self.last_sparse = None
+        if compression is not None and compression.sparse:
+            from .sparse import SparsePlan
+            self._sparse = SparsePlan(self._cplan, compression.sparsity_ratio).empty(
+                len(self.slots))
         self.exact = bool(exact) and self.distributed
         if self.exact:
             self._init_exact()
@@ -273,6 +289,12 @@ class RankRound:
     def set_global(self, flat: torch.Tensor):
         self.global_flat.copy_(flat)
 
+    def _sparse_sum(self):
+        """Whether this round's parameter aggregate is summed from the sparse payload: the plain
+        FedAvg routes.  Exact mode, a robust rule and central DP read dense rows."""
+        return self._sparse is not None and self.aggregator is None and self.central is None \
+            and not self.exact
+
     def reset_compression_state(self):
         """Forget every client's error-feedback residual (a new training run, or a new
         client-to-slot assignment, on the same RankRound)."""
@@ -310,6 +332,10 @@ class RankRound:
             if self.compression.stochastic:
                 extra.update(key=self._round_key(seed), row_ids=self.slot_ids[:S],
                              words=self.squant_words)
+            if self._sparse is not None:
+                # the plain FedAvg sums straight from the payload: the rows stay as trained
+                extra.update(sparse_out=self._sparse, rewrite_rows=not self._sparse_sum())
+                self.last_sparse = self._sparse
             compress_rows(self._cplan, self.compression, tr.params, S,
                           base=self.global_flat.view(1, -1).expand(S, -1), **extra)
         distributed = self.distributed
@@ -353,11 +379,16 @@ class RankRound:
             if sopt is not None:
                 sopt.step_vector(self.partial, self.global_flat)
         elif self.aggregator is None:
-            if sopt is not None and not distributed:  # weighted sum + step, one launch
-                sopt.step_rows(tr.params, self.w32, self.global_flat, self.rows)
+            if sopt is not None and not distributed and self._sparse is None:
+                sopt.step_rows(tr.params, self.w32, self.global_flat, self.rows)  # one launch
             else:
-                ops.fedavg_weighted_sum(tr.params, self.w32, self.partial, row_index=self.rows,
-                                        P=self.P)
+                if self._sparse is not None:  # the same sum from the (index, value) payload
+                    from .sparse import sparse_fedavg
+                    sparse_fedavg(self._sparse, self.w32, self.global_flat, self.partial,
+                                  row_index=self.rows)
+                else:
+                    ops.fedavg_weighted_sum(tr.params, self.w32, self.partial,
+                                            row_index=self.rows, P=self.P)
                 if distributed:
                     dist.all_reduce(self.partial, op=dist.ReduceOp.SUM, group=self.group)
                 if sopt is None:

@@ -72,6 +72,75 @@ def weight_dicts_to_packed(dicts: Sequence[Dict[str, torch.Tensor]], layout, dev
     return host.to(device)
 
 
+# ------------------------------------------------------------------ sparse top-k payloads
+def sparse_to_payloads(updates, layout, nclients: int) -> List[Dict]:
+    """The clients' top-k uploads as TopKSparsificationCompressor.compress builds them
+    (compression.py:262-297), from device payload rows (fedhip.sparse.SparseUpdates) with ONE
+    D2H copy.  Per client ``{'compressed_weights': {name: {'values': fp32 [k], 'indices':
+    int64 [k]}}, 'metadata': {...}}``; the indices are flat and ascending (D15)."""
+    sp = updates.plan
+    K = sp.K
+    host = torch.stack([updates.idx[:nclients, :K],
+                        updates.val[:nclients, :K].view(torch.int32)]).to("cpu")
+    idx, val = host[0].to(torch.int64), host[1].view(torch.float32)
+    ratio = max(0.0, min(1.0, sp.ratio))
+    out = []
+    for z in range(nclients):
+        cw, params = {}, {}
+        for s, (n, shape) in enumerate(zip(layout.names, layout.shapes)):
+            a, b = sp.koff_host[s], sp.koff_host[s + 1]
+            cw[n] = {"values": val[z, a:b].clone(), "indices": idx[z, a:b].clone()}
+            params[n] = {"original_shape": torch.Size(shape), "original_dtype": "torch.float32",
+                         "sparsity_ratio": ratio}
+        out.append({"compressed_weights": cw,
+                    "metadata": {"algorithm": f"topk_sparsification_{ratio}",
+                                 "sparsity_ratio": ratio, "sparsification_params": params}})
+    return out
+
+
+def sort_segment(indices: torch.Tensor, values: torch.Tensor):
+    """One layer's received (indices, values) in ascending index order (the reference ships
+    them in magnitude order); stable, so equal indices stay for validation to flag."""
+    order = torch.sort(indices.reshape(-1).to(torch.int64), stable=True).indices
+    return indices.reshape(-1)[order], values.reshape(-1)[order]
+
+
+def payloads_to_sparse(payloads: Sequence[Dict], layout, plan, device):
+    """Received top-k uploads -> validated device payload rows (one H2D copy).  payloads: per
+    client the ``compressed_weights`` dict, or a dict holding it under that key (what
+    sparse_to_payloads returns); plan: the fedhip.sparse.SparsePlan of the layout and ratio.
+    Indices may come in any order.  A layer with a wrong k, or one fh_sparse_validate flags
+    (index out of range, repeated index), raises FedHipError naming client and layer before any
+    consumer sees the payload."""
+    from .sparse import SparseUpdates, sparse_validate
+    K, C = plan.K, len(payloads)
+    stride = (K + 3) // 4 * 4
+    host = torch.zeros(2, max(C, 1), stride, dtype=torch.int32)
+    lim = 2 ** 31 - 1
+    for z, p in enumerate(payloads):
+        cw = p.get("compressed_weights", p)
+        for s, n in enumerate(layout.names):
+            a, b = plan.koff_host[s], plan.koff_host[s + 1]
+            if n not in cw:
+                raise ops.FedHipError(f"client {z}: layer {n} is missing from the payload")
+            ind, v = cw[n]["indices"], cw[n]["values"]
+            if ind.numel() != b - a or v.numel() != b - a:
+                raise ops.FedHipError(f"client {z}: layer {n} carries {ind.numel()} indices / "
+                                      f"{v.numel()} values, expected k = {b - a}")
+            ind, v = sort_segment(ind, v)
+            # an index no int32 holds is out of range for every layer: keep it so after the cast
+            host[0, z, a:b] = ind.clamp(-1, lim).to(torch.int32)
+            host[1, z, a:b] = v.to(torch.float32).view(torch.int32)
+    dev = host.to(device)
+    upd = SparseUpdates(dev[0, :C, :K], dev[1, :C, :K].view(torch.float32), plan)
+    bad = sparse_validate(upd).to("cpu")
+    if bool(bad.any()):
+        z, s = [int(t) for t in bad.nonzero()[0]]
+        raise ops.FedHipError(f"client {z}: layer {layout.names[s]} has indices outside "
+                              f"[0, {plan.plan.lengths[s]}) or repeated")
+    return upd
+
+
 def weight_change_metrics(current: torch.Tensor, previous: torch.Tensor,
                           seg_offsets: torch.Tensor) -> Dict[str, float]:
     """{'norm': ||current - previous||, 'relative': norm / ||current||} over the layers

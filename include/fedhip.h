@@ -36,6 +36,9 @@
  *   fh_topk_rows             TopKSparsificationCompressor (compression.py:250-368)
  *   fh_ef_fold / fh_ef_topk_finish / fh_ef_quant_finish / fh_squant_rows
  *                            not in the reference (error feedback, stochastic rounding)
+ *   fh_topk_pack_rows / fh_sparse_validate / fh_sparse_unpack_rows / fh_sparse_fedavg
+ *                            TopKSparsificationCompressor's {'values', 'indices'} payload
+ *                            (compression.py:262-297, 346-365) and FedAvg straight from it
  */
 #ifndef FEDHIP_H_
 #define FEDHIP_H_
@@ -1093,6 +1096,72 @@ int fh_squant_rows(const float* x, int64_t x_cs, const float* base, int64_t base
                    int32_t nseg, int32_t nchunks, int32_t bits, int32_t symmetric, uint64_t key,
                    const int64_t* ids, const uint32_t* words, int64_t words_cs, float* scale_out,
                    float* lo_out, void* ws, size_t ws_bytes, void* stream);
+
+/* ---------------- sparse top-k updates (compression.py:262-365) -----
+ * What TopKSparsificationCompressor ships per layer, {'values', 'indices'}, as packed rows, and
+ * the aggregation from it.  Conventions of the two blocks above: packed rows with element
+ * strides, segments by seg_offsets / chunk_offsets, nothing outside
+ * [seg_offsets[0], seg_offsets[nseg]) of a parameter row is read or written, one launch (pack:
+ * two) for all clients.  fl32() marks one rounded fp32 operation; none is ever fused.
+ *
+ * Payload.  koff (device int32[nseg+1]) is the exclusive prefix sum of seg_k and K = koff[nseg].
+ * Client z's payload is idx[z][0..K) (int32, segment-local flat index) and val[z][0..K) (fp32);
+ * segment s occupies [koff[s], koff[s+1]) with indices STRICTLY ASCENDING.  Nothing outside
+ * [0, K) of a payload row is read or written.
+ *
+ * fh_topk_pack_rows      ordered compaction of the uint8 keep mask fh_topk_rows wrote.  For every
+ *                        element i of segment s with keep[z][i] != 0, in ascending i:
+ *                          idx = i - seg_offsets[s],  val = v,
+ *                          v = fl32(x[z][i] - base[z][i])   (base NULL: v = x[z][i]; base_cs 0
+ *                        broadcasts one row) — the v fh_topk_rows ranked.  count_out (nullable,
+ *                        int32 [nclients][nseg]) gets the number of kept elements found
+ *                        (= seg_k[s] for finite input).  Slots of a segment beyond its count are
+ *                        left untouched; kept elements beyond koff[s+1] - koff[s] are counted and
+ *                        not written.  Positions come from per-(chunk, client) counts, their sum
+ *                        over the segment's earlier chunks and a wave ballot / prefix popcount:
+ *                        no atomics, the output is deterministic.
+ *                        ws: fh_topk_pack_workspace(nclients, nchunks) bytes.
+ * fh_sparse_validate     bad_out[z][s] (int32 [nclients][nseg]) = 1 when segment s of client z
+ *                        holds an index < 0, an index >= seg_lens[s] (device int64[nseg]) or a
+ *                        neighbouring pair that is not strictly ascending, else 0.  Integer
+ *                        compares on idx alone.  The two consumers below take VALIDATED payloads
+ *                        only; on any other payload their result is unspecified (they still
+ *                        write nothing outside the rows' covered range).
+ * fh_sparse_unpack_rows  _desparsify_tensor plus the base:
+ *                          d[z][i] = val[z][p] where idx[z][p] names i, +0.0 elsewhere,
+ *                          out[z][i] = fl32(base[z][i] + d[z][i])   (base NULL: d[z][i]).
+ *                        That is fh_topk_rows' own out (a base of -0.0 comes out +0.0 where
+ *                        nothing is kept).  out may alias base only when base_cs != 0.
+ * fh_sparse_fedavg       base is ONE row (the global model), out one row, neither aliasing the
+ *                        other.  For every j of the covered range
+ *                          acc = accumulate ? out[j] : +0.0
+ *                          for k = 0 .. num_clients-1, r = row_index[k] (NULL: k):
+ *                            xk  = fl32(base[j] + d[r][j])
+ *                            acc = fl32(acc + fl32(weights[k] * xk))
+ *                          out[j] = acc
+ *                        — bit for bit fh_fedavg_weighted_sum over the rows
+ *                        fh_sparse_unpack_rows(base broadcast) would write, without them.
+ *                        Bytes moved: 8 per payload entry, 8 per parameter. */
+int64_t fh_topk_pack_workspace(int32_t nclients, int32_t nchunks);
+int fh_topk_pack_rows(const float* x, int64_t x_cs, const float* base, int64_t base_cs,
+                      const uint8_t* keep, int64_t keep_cs, int32_t* idx, int64_t idx_cs,
+                      float* val, int64_t val_cs, int32_t* count_out, int32_t nclients,
+                      const int64_t* seg_offsets, const int32_t* chunk_offsets,
+                      const int32_t* koff, int32_t nseg, int32_t nchunks, void* ws,
+                      size_t ws_bytes, void* stream);
+int fh_sparse_validate(const int32_t* idx, int64_t idx_cs, int32_t nclients,
+                       const int64_t* seg_lens, const int32_t* koff, int32_t nseg,
+                       int32_t* bad_out, void* stream);
+int fh_sparse_unpack_rows(const int32_t* idx, int64_t idx_cs, const float* val, int64_t val_cs,
+                          const float* base, int64_t base_cs, float* out, int64_t out_cs,
+                          int32_t nclients, const int64_t* seg_offsets,
+                          const int32_t* chunk_offsets, const int32_t* koff, int32_t nseg,
+                          int32_t nchunks, void* stream);
+int fh_sparse_fedavg(const int32_t* idx, int64_t idx_cs, const float* val, int64_t val_cs,
+                     const int32_t* row_index, const float* weights, int32_t num_clients,
+                     const float* base, const int64_t* seg_offsets, const int32_t* chunk_offsets,
+                     const int32_t* koff, int32_t nseg, int32_t nchunks, float* out,
+                     int32_t accumulate, void* stream);
 
 /* ---------------- evaluation metrics (training.py:214-242, 307-360) ----------
  * Eval-mode metrics of [nclients][batch][K] logits: per image the first-index
