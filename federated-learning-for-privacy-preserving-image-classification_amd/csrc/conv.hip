@@ -20,6 +20,7 @@
 // v_mfma_f32_32x32x2_f32 (exact fp32, 64 cyc/SIMD) is the MAC engine; each
 // wave owns an FM x FN grid of 32x32 accumulators.
 #include "fh_common.h"
+#include "optim_elem.h"
 #include "splitbn.h"
 
 #include <cstdlib>
@@ -3238,11 +3239,32 @@ linear_dgrad_skinny_kernel(const float* __restrict__ dY, int64_t dy_cs, const fl
 // the reduction is only the images, so the layer is a write stream of dW.  One wave = one
 // 32 (m) x 32 (k) tile from 16 MFMAs over the 32 image pairs; a workgroup = 32 m x 128 k.
 // Bias: the k-tile-0 workgroups, one lane per m, images in order.
+//
+// UPD != 0 (1 SGD, 2 Adam / AdamW): the optimizer update applied where the gradient is
+// produced.  The lane that would store a dW (or db) element instead applies opt_apply1 —
+// opt_apply4's operations, optim_elem.h — to that element of the parameter and state rows,
+// in the same 128-B row pieces as the dW stores; dW / db are neither written nor read (the
+// optimizer launch skips the range).  The element's p and state loads are issued before the
+// image operands, so they are in flight with the MFMA chain.  A client with count 0 gets the
+// update on a zero gradient, as the optimizer launch gives it.  The launch must come after
+// the layer's DGRAD, which reads the same weights.
+struct LinUpd {
+    float* pw;          // parameter rows of the weight [client][M][K] ...
+    int64_t pw_cs;
+    float* pb;          // ... and of the bias [client][M] (used when db is given)
+    int64_t pb_cs;
+    float *s1w, *s1b;   // momentum / exp_avg at the parameters' strides (null: SGD, no momentum)
+    float *s2w, *s2b;   // exp_avg_sq (Adam)
+    OptScal o;
+};
+
+template <int UPD = 0>
 __device__ __forceinline__ void linear_wgrad_skinny_body(
         const float* __restrict__ X, int64_t x_cs, const float* __restrict__ dY, int64_t dy_cs,
         float* __restrict__ dW, int64_t dw_cs, float* __restrict__ db, int64_t db_cs,
         const int32_t* __restrict__ counts, int batch, int K, int M, int z, int kblock,
-        int mblock, const float* __restrict__ rowscale = nullptr) {
+        int mblock, const float* __restrict__ rowscale = nullptr,
+        const LinUpd* __restrict__ u = nullptr) {
     // rowscale (nullable, [client][batch]): dY row b scaled by rowscale[z][b] on load — the
     // fp32 products fh_scale_rows would store (DP-SGD's clipped linear-layer sums)
     const int m0 = mblock * 32;
@@ -3264,6 +3286,18 @@ __device__ __forceinline__ void linear_wgrad_skinny_body(
     // loads had put each image pair's loads and MFMA in a basic block of their own, 16
     // dependent round trips per tile
     const float* yzc = dY + z * dy_cs + (mok ? m0 + r32 : 0);
+    [[maybe_unused]] OptIn1 uin[16];
+    [[maybe_unused]] float bc2_sqrt = 0.f, neg_step = 0.f;
+    if constexpr (UPD != 0) {
+        bc2_sqrt = (UPD == 2 && u->o.scal) ? u->o.scal[0] : u->o.bc2_sqrt;
+        neg_step = (UPD == 2 && u->o.scal) ? u->o.scal[1] : u->o.neg_step_size;
+        const int64_t zo = z * u->pw_cs + k0 + r32;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {  // rows past M read row m0 (discarded)
+            const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            opt_load1<UPD == 2>(u->pw, u->s1w, u->s2w, zo + (int64_t)(m < M ? m : m0) * K, uin[r]);
+        }
+    }
     float av[16], bv[16];
 #pragma unroll
     for (int p = 0; p < 16; ++p) {
@@ -3281,11 +3315,22 @@ __device__ __forceinline__ void linear_wgrad_skinny_body(
         const float bb = ok ? bv[p] : 0.f;
         acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, bb, acc, 0, 0, 0);
     }
-    float* wz = dW + z * dw_cs + k0 + r32;
+    if constexpr (UPD != 0) {
+        const int64_t zo = z * u->pw_cs + k0 + r32;
 #pragma unroll
-    for (int r = 0; r < 16; ++r) {
-        const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
-        if (m < M) wz[(int64_t)m * K] = acc[r];
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (m < M)
+                opt_apply1<UPD == 2>(u->pw, u->s1w, u->s2w, zo + (int64_t)m * K, uin[r], acc[r],
+                                     u->o, bc2_sqrt, neg_step);
+        }
+    } else {
+        float* wz = dW + z * dw_cs + k0 + r32;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int m = m0 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            if (m < M) wz[(int64_t)m * K] = acc[r];
+        }
     }
     if (db && kblock == 0 && wid == 0 && h == 0 && mok) {
         // every image's term loaded first, then added in image order (the loop's loads had
@@ -3293,6 +3338,9 @@ __device__ __forceinline__ void linear_wgrad_skinny_body(
         // (r05: from in-bounds addresses, selects after — the conditional loads had sat in
         // branches with their uses under a row scale)
         const float* rsz = rowscale ? rowscale + (int64_t)z * batch : yz;
+        [[maybe_unused]] OptIn1 bin;  // the bias element's p / state, in flight with the terms
+        if constexpr (UPD != 0)
+            opt_load1<UPD == 2>(u->pb, u->s1b, u->s2b, z * u->pb_cs + m0 + r32, bin);
         float t[32], sc[32];
 #pragma unroll
         for (int b = 0; b < 32; ++b) {
@@ -3306,7 +3354,11 @@ __device__ __forceinline__ void linear_wgrad_skinny_body(
 #pragma unroll
         for (int b = 0; b < 32; ++b)
             if (b < cnt) v += t[b];
-        db[z * db_cs + m0 + r32] = v;
+        if constexpr (UPD != 0)
+            opt_apply1<UPD == 2>(u->pb, u->s1b, u->s2b, z * u->pb_cs + m0 + r32, bin, v, u->o,
+                                 bc2_sqrt, neg_step);
+        else
+            db[z * db_cs + m0 + r32] = v;
     }
 }
 
@@ -3326,6 +3378,23 @@ linear_wgrad_skinny_kernel(const float* __restrict__ X, int64_t x_cs, const floa
     const int kb = b % gx, rest = b / gx;
     linear_wgrad_skinny_body(X, x_cs, dY, dy_cs, dW, dw_cs, db, db_cs, counts, batch, K, M,
                              rest / gy, kb, rest % gy, rowscale);
+}
+
+// linear_wgrad_skinny_kernel with the optimizer update in its epilogue (UPD 1 SGD, 2 Adam):
+// the same grid, the same XCD-aware order, the same tiles.  db != null only says "with bias".
+template <int UPD>
+__global__ void __launch_bounds__(256)
+linear_wgrad_upd_kernel(const float* __restrict__ X, int64_t x_cs, const float* __restrict__ dY,
+                        int64_t dy_cs, const float* __restrict__ db,
+                        const int32_t* __restrict__ counts, int batch, int K, int M,
+                        const LinUpd u) {
+    const int gx = gridDim.x, gy = gridDim.y;
+    const int N = gx * gy * gridDim.z;
+    int b = blockIdx.x + gx * (blockIdx.y + gy * blockIdx.z);
+    if ((N & 7) == 0) b = (b & 7) * (N >> 3) + (b >> 3);
+    const int kb = b % gx, rest = b / gx;
+    linear_wgrad_skinny_body<UPD>(X, x_cs, dY, dy_cs, nullptr, 0, const_cast<float*>(db), 0,
+                                  counts, batch, K, M, rest / gy, kb, rest % gy, nullptr, &u);
 }
 
 // Several linear layers' weight gradients in one launch (r05, DP-SGD's pass 2: fc2's and
@@ -3685,7 +3754,10 @@ static int linear_bwd_fused_impl(const float* x, int64_t x_cs, const float* dy, 
                                  const float* w, int64_t w_cs, float* dw, int64_t dw_cs,
                                  float* db, int64_t db_cs, float* dx, int64_t dx_cs,
                                  const SkinnyBwdEpi& ep, const int32_t* counts, int32_t nclients,
-                                 int32_t batch, int32_t in_f, int32_t out_f, void* stream) {
+                                 int32_t batch, int32_t in_f, int32_t out_f, void* stream,
+                                 const fh_linear_update* upd = nullptr,
+                                 int32_t* applied = nullptr) {
+    if (applied) *applied = 0;
     if (nclients == 0) return FH_OK;
     FH_REQUIRE(x && dy && w && dw && dx, "linear_bwd_fused: null pointer");
     if (!(batch <= 32 && in_f % (kSkinny32 ? 32 : 128) == 0 && out_f % 32 == 0 &&
@@ -3696,7 +3768,42 @@ static int linear_bwd_fused_impl(const float* x, int64_t x_cs, const float* dy, 
     }
     const int kb = (int)ceil_div(in_f, 128);  // WGRAD k-blocks (spare waves return)
     const int nw = kb * (int)ceil_div(out_f, 32);
-    if (kLinearSkinny != 2 && in_f % 128 == 0 && (int64_t)kb * nclients >= fill(256)) {
+    const bool wide = kLinearSkinny != 2 && in_f % 128 == 0 && (int64_t)kb * nclients >= fill(256);
+    if (upd && (wide || upd->mode == 2)) {
+        // the update applied in the WGRAD epilogue: DGRAD first — it reads the weights the
+        // WGRAD launch overwrites — with the tile shape this width's DGRAD role has today
+        FH_REQUIRE(upd->pw && (upd->adam ? upd->s1w && upd->s2w : upd->momentum == 0.0 || upd->s1w),
+                   "linear_bwd_fused_upd: null parameter / state rows");
+        FH_REQUIRE(!db || (upd->pb && (upd->adam ? upd->s1b && upd->s2b
+                                                 : upd->momentum == 0.0 || upd->s1b)),
+                   "linear_bwd_fused_upd: null bias parameter / state rows");
+        LinUpd u{upd->pw, upd->pw_cs, upd->pb, upd->pb_cs, upd->s1w, upd->s1b, upd->s2w, upd->s2b,
+                 upd->adam ? adam_scalars(upd->lr, upd->beta1, upd->beta2, upd->eps,
+                                          upd->weight_decay, upd->decoupled, upd->step_size,
+                                          upd->bc2_sqrt, upd->scal_dev)
+                           : sgd_scalars((float)upd->lr, (float)upd->momentum,
+                                         (float)upd->weight_decay, upd->first_step)};
+        if (wide)
+            FH_LAUNCH(linear_dgrad_skinny_kernel<4>, dim3((unsigned)(in_f / 128), nclients),
+                      dim3(256), 0, as_stream(stream), dy, dy_cs, w, w_cs, dx, dx_cs, counts,
+                      batch, in_f, out_f, ep);
+        else
+            FH_LAUNCH(linear_dgrad_skinny_kernel<1>, dim3((unsigned)(in_f / 32), nclients),
+                      dim3(256), 0, as_stream(stream), dy, dy_cs, w, w_cs, dx, dx_cs, counts,
+                      batch, in_f, out_f, ep);
+        FH_LAUNCH_CHECK("linear_bwd_fused_upd dgrad");
+        const dim3 grid((unsigned)kb, (unsigned)ceil_div(out_f, 32), nclients);
+        if (upd->adam)
+            FH_LAUNCH(linear_wgrad_upd_kernel<2>, grid, dim3(256), 0, as_stream(stream), x, x_cs,
+                      dy, dy_cs, (const float*)db, counts, batch, in_f, out_f, u);
+        else
+            FH_LAUNCH(linear_wgrad_upd_kernel<1>, grid, dim3(256), 0, as_stream(stream), x, x_cs,
+                      dy, dy_cs, (const float*)db, counts, batch, in_f, out_f, u);
+        FH_LAUNCH_CHECK("linear_bwd_fused_upd wgrad");
+        *applied = 1;
+        return FH_OK;
+    }
+    if (wide) {
         // wide launches: the two roles as two kernels — in one grid every WGRAD workgroup
         // would carry the DGRAD role's 48 KB of LDS and stream dW at 3 workgroups per CU
         // (fc1 at 32 clients: 190 us fused vs ~105 us as two launches).  SimpleCNN's fc1
@@ -3756,6 +3863,47 @@ extern "C" int fh_linear_bwd_fused_pool(const float* x, int64_t x_cs, const floa
     const SkinnyBwdEpi ep{nullptr, 0, 1.f, x, x_cs, pidx, pi_cs, OW, OH * OW, xh, xw};
     return linear_bwd_fused_impl(x, x_cs, dy, dy_cs, w, w_cs, dw, dw_cs, db, db_cs, dx, dx_cs, ep,
                                  counts, nclients, batch, C * OH * OW, out_f, stream);
+}
+
+static int check_linear_update(const fh_linear_update* upd, const int32_t* applied) {
+    FH_REQUIRE(upd && applied, "linear_bwd_fused_upd: null update / applied");
+    FH_REQUIRE(upd->mode == 1 || upd->mode == 2, "linear_bwd_fused_upd: mode %d", upd->mode);
+    return FH_OK;
+}
+
+extern "C" int fh_linear_bwd_fused_upd(const float* x, int64_t x_cs, const float* dy,
+                                       int64_t dy_cs, const float* w, int64_t w_cs, float* dw,
+                                       int64_t dw_cs, float* db, int64_t db_cs, float* dx,
+                                       int64_t dx_cs, const uint8_t* mask, int64_t m_cs,
+                                       float p_drop, const float* relu_ref, int64_t r_cs,
+                                       const int32_t* counts, int32_t nclients, int32_t batch,
+                                       int32_t in_f, int32_t out_f, const fh_linear_update* upd,
+                                       int32_t* applied, void* stream) {
+    FH_REQUIRE(nclients >= 0 && batch > 0 && in_f > 0 && out_f > 0,
+               "linear_bwd_fused_upd: bad shape");
+    FH_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "linear_bwd_fused_upd: p=%g", p_drop);
+    if (const int rc = check_linear_update(upd, applied)) return rc;
+    const SkinnyBwdEpi ep{mask, m_cs, 1.0f / (1.0f - p_drop), relu_ref, r_cs, nullptr, 0, 1, 1, 0, 0};
+    return linear_bwd_fused_impl(x, x_cs, dy, dy_cs, w, w_cs, dw, dw_cs, db, db_cs, dx, dx_cs, ep,
+                                 counts, nclients, batch, in_f, out_f, stream, upd, applied);
+}
+
+extern "C" int fh_linear_bwd_fused_pool_upd(const float* x, int64_t x_cs, const float* dy,
+                                            int64_t dy_cs, const float* w, int64_t w_cs,
+                                            float* dw, int64_t dw_cs, float* db, int64_t db_cs,
+                                            float* dx, int64_t dx_cs, const uint8_t* pidx,
+                                            int64_t pi_cs, const int32_t* counts,
+                                            int32_t nclients, int32_t batch, int32_t C,
+                                            int32_t OH, int32_t OW, int32_t xh, int32_t xw,
+                                            int32_t out_f, const fh_linear_update* upd,
+                                            int32_t* applied, void* stream) {
+    FH_REQUIRE(nclients >= 0 && batch > 0 && C > 0 && OH > 0 && OW > 0 && xh >= 2 * OH &&
+               xw >= 2 * OW && out_f > 0, "linear_bwd_fused_pool_upd: bad shape");
+    FH_REQUIRE(pidx || nclients == 0, "linear_bwd_fused_pool_upd: null argmax");
+    if (const int rc = check_linear_update(upd, applied)) return rc;
+    const SkinnyBwdEpi ep{nullptr, 0, 1.f, x, x_cs, pidx, pi_cs, OW, OH * OW, xh, xw};
+    return linear_bwd_fused_impl(x, x_cs, dy, dy_cs, w, w_cs, dw, dw_cs, db, db_cs, dx, dx_cs, ep,
+                                 counts, nclients, batch, C * OH * OW, out_f, stream, upd, applied);
 }
 
 extern "C" size_t fh_linear_wgrad_workspace(int32_t nclients, int32_t batch, int32_t in_f,

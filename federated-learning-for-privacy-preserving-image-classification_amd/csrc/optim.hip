@@ -11,6 +11,7 @@
 // The optimizer is re-created every round (training.py:89), so callers pass
 // first_step / step counts that restart at 1 each round.
 #include "fh_common.h"
+#include "optim_elem.h"
 
 namespace fh {
 
@@ -35,16 +36,7 @@ sgd_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict
 
 // The same update, four parameters per lane (16-B loads/stores; rows are 256-B aligned and
 // padded to 64 floats, so packed slabs always qualify).  Per-element arithmetic is the
-// scalar kernel's, so both give identical bits.
-__device__ __forceinline__ float sgd_elem(float pv, float gv, float bv, float neg_lr, float mom,
-                                          float wd, int first, float& b_out) {
-    if (wd != 0.f) gv = fmaf(pv, wd, gv);
-    float b = gv;
-    if (mom != 0.f) b = first ? gv : (bv * mom + gv);
-    b_out = b;
-    return fmaf(b, neg_lr, pv);
-}
-
+// scalar kernel's (sgd_elem / adam_elem, optim_elem.h), so both give identical bits.
 __global__ void __launch_bounds__(256)
 sgd4_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __restrict__ buf,
             int64_t n4, float neg_lr, float mom, float wd, int first) {
@@ -62,24 +54,6 @@ sgd4_kernel(float4* __restrict__ p, const float4* __restrict__ g, float4* __rest
         if (use_buf) buf[i] = b;
         p[i] = o;
     }
-}
-
-// One Adam/AdamW element in torch.optim's rounding order; shared by the scalar and the
-// float4 kernel so the two give identical bits.
-__device__ __forceinline__ float adam_elem(float pv, float gv, float& m, float& v, float wd,
-                                          float decay_mul, int decoupled, float one_m_b1,
-                                          float b2, float one_m_b2, float bc2_sqrt, float eps,
-                                          float neg_step_size) {
-    if (wd != 0.f) {
-        if (decoupled) pv = pv * decay_mul;
-        else gv = fmaf(pv, wd, gv);
-    }
-    const float mv = fmaf(one_m_b1, gv - m, m);
-    const float vv = v * b2 + (one_m_b2 * gv) * gv;
-    m = mv;
-    v = vv;
-    const float denom = sqrtf(vv) / bc2_sqrt + eps;
-    return pv + neg_step_size * (mv / denom);
 }
 
 __global__ void __launch_bounds__(256)
@@ -141,14 +115,6 @@ struct SlabRanges {
     int n;
     SlabRange r[2 * FH_MAX_GRAD_SLABS + 1];
 };
-struct OptScal {  // SGD: neg_lr, mom, wd, first | Adam: the adam_elem scalars
-    float neg_lr, mom, wd;
-    int first;
-    float decay_mul, one_m_b1, b2, one_m_b2, bc2_sqrt, eps, neg_step_size;
-    int decoupled;
-    const float* scal;  // Adam: device {bc2_sqrt, -step_size} or null
-};
-
 constexpr int kOptPlainPer = 1024;  // float4s per plain block
 
 // DP-SGD (r04): the same launch finishes a per-sample-clipped step.  Slab ranges hold one
@@ -177,49 +143,6 @@ __device__ __forceinline__ void dp_noise4(float4& g, const OptDp& d, uint64_t ke
     if (j + 1 < d.n_noise) g.y = g.y + s * r[1];
     if (j + 2 < d.n_noise) g.z = g.z + s * r[2];
     if (j + 3 < d.n_noise) g.w = g.w + s * r[3];
-}
-
-// The update of one float4 in two phases: opt_load4 issues its loads (p and the state, from
-// in-bounds addresses — a missing momentum buffer reads p — so no load sits under a branch),
-// opt_apply4 computes and stores.  The plain ranges load all their float4s first (r05: with
-// the momentum load under `if (use_buf)` each float4's loads and update were one dependent
-// round trip).
-struct OptIn {
-    float4 p, m, v;
-};
-template <bool ADAM>
-__device__ __forceinline__ void opt_load4(const float4* p, const float4* s1, const float4* s2,
-                                          int64_t i, OptIn& in) {
-    in.p = p[i];
-    in.m = (s1 ? s1 : p)[i];
-    if constexpr (ADAM) in.v = s2[i];
-}
-
-template <bool ADAM>
-__device__ __forceinline__ void opt_apply4(float4* p, float4* s1, float4* s2, int64_t i,
-                                           const OptIn& in, float4 gv, const OptScal& o,
-                                           float bc2_sqrt, float neg_step) {
-    const float4 pv = in.p;
-    float4 out;
-    if constexpr (!ADAM) {
-        const bool use_buf = o.mom != 0.f;
-        const float4 bv = (use_buf && !o.first) ? in.m : make_float4(0.f, 0.f, 0.f, 0.f);
-        float4 b;
-        out.x = sgd_elem(pv.x, gv.x, bv.x, o.neg_lr, o.mom, o.wd, o.first, b.x);
-        out.y = sgd_elem(pv.y, gv.y, bv.y, o.neg_lr, o.mom, o.wd, o.first, b.y);
-        out.z = sgd_elem(pv.z, gv.z, bv.z, o.neg_lr, o.mom, o.wd, o.first, b.z);
-        out.w = sgd_elem(pv.w, gv.w, bv.w, o.neg_lr, o.mom, o.wd, o.first, b.w);
-        if (use_buf) s1[i] = b;
-    } else {
-        float4 mv = in.m, vv = in.v;
-#define FH_ADAM_LANE(c) out.c = adam_elem(pv.c, gv.c, mv.c, vv.c, o.wd, o.decay_mul, o.decoupled, \
-                                          o.one_m_b1, o.b2, o.one_m_b2, bc2_sqrt, o.eps, neg_step)
-        FH_ADAM_LANE(x); FH_ADAM_LANE(y); FH_ADAM_LANE(z); FH_ADAM_LANE(w);
-#undef FH_ADAM_LANE
-        s1[i] = mv;
-        s2[i] = vv;
-    }
-    p[i] = out;
 }
 
 template <bool ADAM, bool DP = false>
@@ -386,12 +309,15 @@ static int build_ranges(const fh_grad_slab* slabs, int nslabs, int64_t row_len, 
     };
     for (int i = 0; i < nslabs; ++i) {
         const fh_grad_slab& s = slabs[i];
+        // an applied range (updated upstream) has no slab; it tiles the row like any other
         FH_REQUIRE(s.off >= pos && s.len > 0 && s.off + s.len <= row_len && s.off % 4 == 0 &&
-                       s.len % 4 == 0 && s.slab && (uintptr_t)s.slab % 16 == 0 && s.splits >= 1,
-                   "step_slabs: bad slab range %d (off %lld len %lld splits %d)", i,
-                   (long long)s.off, (long long)s.len, s.splits);
+                       s.len % 4 == 0 &&
+                       (s.applied ? !s.slab && s.splits == 0 && !per_image
+                                  : s.slab && (uintptr_t)s.slab % 16 == 0 && s.splits >= 1),
+                   "step_slabs: bad slab range %d (off %lld len %lld splits %d applied %d)", i,
+                   (long long)s.off, (long long)s.len, s.splits, s.applied);
         if (s.off > pos) add(pos, s.off - pos, nullptr, 0);
-        add(s.off, s.len, s.slab, s.splits);
+        if (!s.applied) add(s.off, s.len, s.slab, s.splits);  // applied: no blocks, no access
         pos = s.off + s.len;
     }
     if (pos < row_len) add(pos, row_len - pos, nullptr, 0);
@@ -418,11 +344,8 @@ extern "C" int fh_sgd_step_slabs(float* param, float* grad, float* momentum_buf,
     SlabRanges rg;
     int blocks = 0;
     if (const int rc = build_ranges(slabs, nslabs, row_len, rg, blocks)) return rc;
-    OptScal o{};
-    o.neg_lr = -lr;
-    o.mom = momentum;
-    o.wd = weight_decay;
-    o.first = first_step;
+    if (blocks == 0) return FH_OK;  // every range was applied upstream
+    const OptScal o = sgd_scalars(lr, momentum, weight_decay, first_step);
     FH_LAUNCH(opt_slabs_kernel<false>, dim3(blocks, nclients), dim3(256), 0, as_stream(stream),
               (float4*)param, (float4*)grad, (float4*)momentum_buf, (float4*)nullptr,
               row_stride / 4, rg, o, OptDp{});
@@ -446,18 +369,10 @@ extern "C" int fh_adam_step_slabs(float* param, float* grad, float* exp_avg, flo
     SlabRanges rg;
     int blocks = 0;
     if (const int rc = build_ranges(slabs, nslabs, row_len, rg, blocks)) return rc;
+    if (blocks == 0) return FH_OK;  // every range was applied upstream
     // fh_adam_step's fp32 roundings of the double scalars
-    OptScal o{};
-    o.wd = (float)weight_decay;
-    o.decay_mul = (float)(1.0 - lr * weight_decay);
-    o.decoupled = decoupled;
-    o.one_m_b1 = (float)(1.0 - beta1);
-    o.b2 = (float)beta2;
-    o.one_m_b2 = (float)(1.0 - beta2);
-    o.bc2_sqrt = (float)bc2_sqrt;
-    o.eps = (float)eps;
-    o.neg_step_size = (float)(-step_size);
-    o.scal = scal_dev;
+    const OptScal o = adam_scalars(lr, beta1, beta2, eps, weight_decay, decoupled, step_size,
+                                   bc2_sqrt, scal_dev);
     FH_LAUNCH(opt_slabs_kernel<true>, dim3(blocks, nclients), dim3(256), 0, as_stream(stream),
               (float4*)param, (float4*)grad, (float4*)exp_avg, (float4*)exp_avg_sq,
               row_stride / 4, rg, o, OptDp{});

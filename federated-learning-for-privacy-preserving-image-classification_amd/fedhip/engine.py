@@ -153,6 +153,12 @@ class PackedTrainer:
         # restores the separate reduction launches (tests compare the two bit for bit)
         self.defer_wgrad_reduce = True
         self._slabs = None
+        # the classifier layers' update applied by their weight-gradient launches in the
+        # steps of a round (ops.LinearUpdate; needs defer_wgrad_reduce: the optimizer launch
+        # learns the applied ranges with the slab ranges).  step() keeps the gradient rows
+        # whole — its callers read them (LocalTrainer exposes param.grad).
+        self.fuse_linear_update = True
+        self._fuse_now = False
         # Step graphs: every step after the first of a round is replayed from a HIP graph
         # captured once per (active slots, optimizer, lr, data); the per-step inputs (batch
         # indices, counts, epoch resets, dropout key, Adam bias corrections) are copied into
@@ -252,9 +258,12 @@ class PackedTrainer:
                           weight_decay=0.01 if adamw else 0.0, decoupled=adamw, n=cnt,
                           scal_dev=adam_dev)
 
-    def _step_launches(self, n, counts, reset, first, adam_dev=None):
-        """The kernel sequence of one packed step (no host bookkeeping: graph-capturable)."""
+    def _step_launches(self, n, counts, reset, first, adam_dev=None, fuse_update=False):
+        """The kernel sequence of one packed step (no host bookkeeping: graph-capturable).
+        fuse_update: the linear layers may apply their own update (their gradient rows are
+        then not written)."""
         net = self.net
+        self._fuse_now = fuse_update and self.fuse_linear_update
         ce = dict(loss_out=self.loss_out, acc_loss=self.acc_loss, acc_correct=self.acc_correct,
                   acc_seen=self.acc_seen, reset=reset)
         # (<= 16 classes: the head kernel stages W in LDS; CIFAR-100's 100-class head is
@@ -299,7 +308,15 @@ class PackedTrainer:
         if self._slabs is None:
             self._slabs = ops.GradSlabs(self.device)
         with self._slabs.collect(self.grads) as slabs:
-            self.net.backward(self.params, self.grads, n, counts)
+            if self._fuse_now and ops.FUSE_LINEAR_UPDATE[0]:
+                self.net.lin_update = ops.LinearUpdate(
+                    self.params, self.state1, self.state2, self.opt_type, self.lr,
+                    step=self.opt_step, first_step=first,
+                    weight_decay=0.01 if self.opt_type == "adamw" else 0.0, scal_dev=adam_dev)
+            try:
+                self.net.backward(self.params, self.grads, n, counts)
+            finally:
+                self.net.lin_update = None
         self._optimizer_launch(n, first, adam_dev, slabs=slabs)
 
     # ------------------------------------------------------------ one packed step
@@ -387,7 +404,7 @@ class PackedTrainer:
                 ops.PROBE.step_images = (int(plan["counts"][g, :n].sum()), self.batch)
             try:
                 self._step_launches(n, views["counts"], views["reset"], first=(g == 0),
-                                    adam_dev=views["adam"])
+                                    adam_dev=views["adam"], fuse_update=True)
             finally:
                 net._src = None
                 ops.PROBE.step_images = None
@@ -492,7 +509,7 @@ class PackedTrainer:
                 try:
                     self._gather(data, labels, views, n, sample_elems)
                     self._step_launches(n, views["counts"], views["reset"], first=False,
-                                        adam_dev=views["adam"])
+                                        adam_dev=views["adam"], fuse_update=True)
                 finally:
                     net._src = None
                     ops.conv_pair_reset()

@@ -149,6 +149,10 @@ class PackedNet:
         # classifier backward: wgrad + dgrad + dropout/ReLU backward in one launch where
         # the layer shape allows (fh_linear_bwd_fused)
         self.fused_linear_bwd = True
+        # ... and the optimizer update of the layer's weight and bias applied by its
+        # weight-gradient launch (ops.LinearUpdate, set by the trainer for the steps it issues
+        # inside a GradSlabs scope; None: the gradient is written for the optimizer launch)
+        self.lin_update = None
         self._head_done = False
         self._head = True
         # SimpleCNN: the 14x14 conv runs on 16x16 planes (the map in the top-left corner,
@@ -408,11 +412,13 @@ class PackedNet:
         # the ReLU mask = p2 > 0): no pooled gradient tensor, no maxpool2_bwd launch
         if not (self.fused_linear_bwd and self.fuse_pool2_bwd and ops.linear_bwd_fused_pool(
                 A("p2", 64, 7, 7), dh1, W(P_, "fc1.weight"), W(G, "fc1.weight"),
-                W(G, "fc1.bias"), da2, i2, n, B, 64, 7, 7, 128, counts=cnt)):
+                W(G, "fc1.bias"), da2, i2, n, B, 64, 7, 7, 128, counts=cnt,
+                update=self.lin_update)):
             dp2 = A("dp2", 64, 7, 7)
             if not (self.fused_linear_bwd and ops.linear_bwd_fused(
                     A("p2", 64, 7, 7), dh1, W(P_, "fc1.weight"), W(G, "fc1.weight"),
-                    W(G, "fc1.bias"), dp2, n, B, 3136, 128, counts=cnt)):
+                    W(G, "fc1.bias"), dp2, n, B, 3136, 128, counts=cnt,
+                    update=self.lin_update)):
                 ops.linear_wgrad(A("p2", 64, 7, 7), dh1, W(G, "fc1.weight"), W(G, "fc1.bias"), n,
                                  B, 3136, 128, counts=cnt)
                 ops.linear_dgrad(dh1, W(P_, "fc1.weight"), dp2, n, B, 3136, 128, counts=cnt)
@@ -686,7 +692,8 @@ class PackedNet:
         m1 = A("m_fc1", 512, dtype=torch.uint8) if dm else None
         if not (self.fused_linear_bwd and ops.linear_bwd_fused(
                 self._e1, dh2, W(P_, "fc2.weight"), W(G, "fc2.weight"), W(G, "fc2.bias"), dh1, n,
-                B, 512, 256, mask=m1, p_drop=p, relu_ref=self._e1, counts=cnt)):
+                B, 512, 256, mask=m1, p_drop=p, relu_ref=self._e1, counts=cnt,
+                update=self.lin_update)):
             ops.linear_wgrad(self._e1, dh2, W(G, "fc2.weight"), W(G, "fc2.bias"), n, B, 512, 256,
                              counts=cnt)
             de1 = A("de1", 512)
@@ -697,7 +704,7 @@ class PackedNet:
         dq = A("dq_conv6", 128, 4, 4)
         if not (self.fused_linear_bwd and ops.linear_bwd_fused(
                 q3, dh1, W(P_, "fc1.weight"), W(G, "fc1.weight"), W(G, "fc1.bias"), dq, n, B,
-                2048, 512, counts=cnt)):
+                2048, 512, counts=cnt, update=self.lin_update)):
             ops.linear_wgrad(q3, dh1, W(G, "fc1.weight"), W(G, "fc1.bias"), n, B, 2048, 512,
                              counts=cnt)
             ops.linear_dgrad(dh1, W(P_, "fc1.weight"), dq, n, B, 2048, 512, counts=cnt)

@@ -662,7 +662,7 @@ def conv2d_c1_pool_wgrad(x, dpool, idx, y, dw, db, nclients, batch, h, wd, cout,
 class FhGradSlab(ctypes.Structure):
     """include/fedhip.h fh_grad_slab."""
     _fields_ = [("off", ctypes.c_int64), ("len", ctypes.c_int64), ("slab", ctypes.c_void_p),
-                ("splits", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+                ("splits", ctypes.c_int32), ("applied", ctypes.c_int32)]
 
 
 MAX_GRAD_SLABS = 24  # FH_MAX_GRAD_SLABS
@@ -846,26 +846,116 @@ def linear_wgrad(x, dy, dw, db, nclients, batch, in_f, out_f, counts=None):
 _SKINNY_IN = 32
 
 
+# The optimizer update of a classifier layer applied in its weight-gradient launch
+# (fh_linear_bwd_fused_upd): 1 = at the widths where the backward already runs as two launches
+# (the narrow dual-role launch keeps its optimizer range), 2 = at every width, 0 = never (the
+# gradient is written and the optimizer launch reads it back).  FH_FUSE_LINEAR_UPDATE sets it.
+FUSE_LINEAR_UPDATE = [int(os.environ.get("FH_FUSE_LINEAR_UPDATE", "1"))]
+LINEAR_UPDATES = [0]  # layers whose update was applied upstream so far (tests, diagnostics)
+
+
+class FhLinearUpdate(ctypes.Structure):
+    """include/fedhip.h fh_linear_update."""
+    _fields_ = [("pw", ctypes.c_void_p), ("pw_cs", ctypes.c_int64), ("pb", ctypes.c_void_p),
+                ("pb_cs", ctypes.c_int64), ("s1w", ctypes.c_void_p), ("s1b", ctypes.c_void_p),
+                ("s2w", ctypes.c_void_p), ("s2b", ctypes.c_void_p), ("adam", ctypes.c_int32),
+                ("decoupled", ctypes.c_int32), ("first_step", ctypes.c_int32),
+                ("mode", ctypes.c_int32), ("lr", ctypes.c_double), ("momentum", ctypes.c_double),
+                ("weight_decay", ctypes.c_double), ("beta1", ctypes.c_double),
+                ("beta2", ctypes.c_double), ("eps", ctypes.c_double),
+                ("step_size", ctypes.c_double), ("bc2_sqrt", ctypes.c_double),
+                ("scal_dev", ctypes.c_void_p)]
+
+
+class LinearUpdate:
+    """The step's optimizer, handed to linear_bwd_fused so that it applies the update to the
+    layer's weight and bias itself: the packed parameter / state rows and the scalars of
+    sgd_step_slabs (opt "sgd") or adam_step_slabs ("adam" / "adamw")."""
+
+    def __init__(self, params, state1, state2, opt, lr, step=1, first_step=False, momentum=0.9,
+                 weight_decay=0.0, scal_dev=None, mode=None):
+        self.params, self.state1, self.state2 = params, state1, state2
+        self.opt, self.lr, self.step, self.first_step = opt, float(lr), step, bool(first_step)
+        self.momentum, self.weight_decay, self.scal_dev = momentum, weight_decay, scal_dev
+        self.mode = FUSE_LINEAR_UPDATE[0] if mode is None else mode
+
+    def struct(self, d, w, dw, db, n_w, n_b):
+        """fh_linear_update for the layer whose gradient views are dw / db, plus the row
+        offsets of the two ranges; None when the layer cannot fuse (the views are not
+        float4-aligned ranges of the rows being collected, or w is not dw's parameter)."""
+        if self.mode not in (1, 2) or d is None or len(d.ranges) + 2 > MAX_GRAD_SLABS:
+            return None
+        P_ = self.params
+        off_w = d.row_range(dw, n_w)
+        off_b = d.row_range(db, n_b) if db is not None else -1
+        if off_w is None or off_b is None or P_.stride(0) != d.grads.stride(0) or \
+                w.stride(0) != P_.stride(0) or w.data_ptr() != P_.data_ptr() + 4 * off_w:
+            return None
+        adam = self.opt in ("adam", "adamw")
+        u = FhLinearUpdate()
+        u.pw, u.pw_cs = w.data_ptr(), P_.stride(0)
+        u.pb, u.pb_cs = (P_.data_ptr() + 4 * off_b, P_.stride(0)) if db is not None else (None, 0)
+        for name, t in (("s1", self.state1), ("s2", self.state2 if adam else None)):
+            if t is not None and t.stride(0) != P_.stride(0):
+                return None
+            setattr(u, name + "w", t.data_ptr() + 4 * off_w if t is not None else None)
+            setattr(u, name + "b", t.data_ptr() + 4 * off_b
+                    if t is not None and db is not None else None)
+        u.adam, u.decoupled = int(adam), int(self.opt == "adamw")
+        u.first_step, u.mode = int(self.first_step), self.mode
+        u.lr, u.momentum, u.weight_decay = self.lr, self.momentum, self.weight_decay
+        u.beta1, u.beta2, u.eps = 0.9, 0.999, 1e-8
+        u.step_size, u.bc2_sqrt = adam_bias_corrections(self.step, self.lr)
+        u.scal_dev = ptr(self.scal_dev)
+        return u, off_w, off_b
+
+
+def _linear_upd_call(name, update, w, dw, db, n_w, n_b, head, tail):
+    """Issue fh_linear_bwd_fused[_pool]_upd when `update` can fuse this layer; True when it was
+    issued.  An applied update leaves the layer's ranges with the optimizer launch as
+    'applied' (skipped) ranges."""
+    d = _DEFER
+    us = update.struct(d, w, dw, db, n_w, n_b) if update is not None else None
+    if us is None:
+        return False
+    u, off_w, off_b = us
+    applied = ctypes.c_int32()
+    call(name, *head, *tail, ctypes.byref(u), ctypes.byref(applied), stream_handle())
+    if applied.value:
+        LINEAR_UPDATES[0] += 1
+        d.ranges.append((off_w, n_w, None, 0))
+        if db is not None:
+            d.ranges.append((off_b, n_b, None, 0))
+    return True
+
+
 def linear_bwd_fused(x, dy, w, dw, db, dx, nclients, batch, in_f, out_f, mask=None, p_drop=0.0,
-                     relu_ref=None, counts=None):
+                     relu_ref=None, counts=None, update=None):
     """linear_wgrad + linear_dgrad + dropout_bwd(dx, mask, relu_out) in one launch
     (fh_linear_bwd_fused).  Returns False (nothing issued) when the shape is outside the
-    fused kernel (the caller then issues the three ops)."""
+    fused kernel (the caller then issues the three ops).
+    update (LinearUpdate, inside a GradSlabs.collect scope): the optimizer update of w and the
+    bias applied by the weight-gradient launch where the width allows
+    (fh_linear_bwd_fused_upd); dw / db are then not written and their ranges are marked
+    applied for the optimizer launch."""
     if not (batch <= 32 and in_f % _SKINNY_IN == 0 and out_f % 32 == 0 and dy.data_ptr() % 16 == 0
             and dy.stride(0) % 4 == 0 and w.stride(0) % 4 == 0):
         return False
     ev = PROBE.begin(f"linear_bwd:{in_f}->{out_f}")
-    call("fh_linear_bwd_fused", ptr(x), _cs(x), ptr(dy), _cs(dy), ptr(w), _cs(w), ptr(dw),
-         _cs(dw), ptr(db), _cs(db), ptr(dx), _cs(dx), ptr(mask), _cs(mask), float(p_drop),
-         ptr(relu_ref), _cs(relu_ref), _counts(counts), nclients, batch, in_f, out_f,
-         stream_handle())
+    head = (ptr(x), _cs(x), ptr(dy), _cs(dy), ptr(w), _cs(w), ptr(dw), _cs(dw), ptr(db), _cs(db),
+            ptr(dx), _cs(dx))
+    tail = (ptr(mask), _cs(mask), float(p_drop), ptr(relu_ref), _cs(relu_ref), _counts(counts),
+            nclients, batch, in_f, out_f)
+    if not _linear_upd_call("fh_linear_bwd_fused_upd", update, w, dw, db, in_f * out_f, out_f,
+                            head, tail):
+        call("fh_linear_bwd_fused", *head, *tail, stream_handle())
     PROBE.end(ev, 4.0 * nclients * batch * in_f * out_f,
               _linear_bytes(nclients, batch, in_f, out_f, acts=3, weights=2), nclients)
     return True
 
 
 def linear_bwd_fused_pool(x, dy, w, dw, db, dx, pidx, nclients, batch, C, OH, OW, out_f,
-                          counts=None):
+                          counts=None, update=None):
     """linear_bwd_fused of a layer fed by a flattened 2x2 max-pool output x [C][OH][OW]
     (fh_linear_bwd_fused_pool): dx is the pool INPUT's gradient (planes dx.shape[-2:], map
     2OH x 2OW top-left) routed to the argmax pidx where x > 0 — maxpool2_bwd's output, with
@@ -877,9 +967,12 @@ def linear_bwd_fused_pool(x, dy, w, dw, db, dx, pidx, nclients, batch, C, OH, OW
         return False
     xh, xw = dx.shape[-2], dx.shape[-1]
     ev = PROBE.begin(f"linear_bwd:{in_f}->{out_f}")
-    call("fh_linear_bwd_fused_pool", ptr(x), _cs(x), ptr(dy), _cs(dy), ptr(w), _cs(w), ptr(dw),
-         _cs(dw), ptr(db), _cs(db), ptr(dx), _cs(dx), ptr(pidx), _cs(pidx), _counts(counts),
-         nclients, batch, C, OH, OW, xh, xw, out_f, stream_handle())
+    head = (ptr(x), _cs(x), ptr(dy), _cs(dy), ptr(w), _cs(w), ptr(dw), _cs(dw), ptr(db), _cs(db),
+            ptr(dx), _cs(dx))
+    tail = (ptr(pidx), _cs(pidx), _counts(counts), nclients, batch, C, OH, OW, xh, xw, out_f)
+    if not _linear_upd_call("fh_linear_bwd_fused_pool_upd", update, w, dw, db, in_f * out_f,
+                            out_f, head, tail):
+        call("fh_linear_bwd_fused_pool", *head, *tail, stream_handle())
     PROBE.end(ev, 4.0 * nclients * batch * in_f * out_f,
               _linear_bytes(nclients, batch, in_f, out_f, acts=3, weights=2) +
               4.0 * nclients * batch * 3 * in_f, nclients)
@@ -1392,8 +1485,9 @@ def sgd_step(param, grad, buf, lr, momentum, weight_decay=0.0, first_step=False,
 def _slab_array(ranges):
     rs = sorted(ranges)
     arr = (FhGradSlab * max(1, len(rs)))()
-    for i, (off, ln, p, sp) in enumerate(rs):
+    for i, (off, ln, p, sp) in enumerate(rs):  # p None: applied upstream (LinearUpdate)
         arr[i].off, arr[i].len, arr[i].slab, arr[i].splits = off, ln, p, sp
+        arr[i].applied = int(p is None)
     return arr, len(rs)
 
 

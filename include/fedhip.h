@@ -309,14 +309,18 @@ int fh_adam_step(float* param, const float* grad, float* exp_avg, float* exp_avg
  * elsewhere g is read from grad.  Then every element gets the fh_sgd_step / fh_adam_step
  * update (same bits).  slabs: HOST array (copied into the launch) of nslabs <=
  * FH_MAX_GRAD_SLABS ranges, sorted, non-overlapping, off and len multiples of 4, each slab
- * 16-B aligned with client stride splits * len. */
+ * 16-B aligned with client stride splits * len.
+ * A range with applied != 0 (slab NULL, splits 0) has had its update applied upstream
+ * (fh_linear_bwd_fused_upd): the step neither reads nor writes param, grad or state there and
+ * spends no workgroup on it.  It still takes part in the sorted / non-overlapping checks.
+ * fh_dpsgd_step_slabs refuses such ranges. */
 #define FH_MAX_GRAD_SLABS 24
 typedef struct {
     int64_t off;       /* first float of the range within a row */
     int64_t len;       /* floats */
     const float* slab; /* device [client][split][len] */
     int32_t splits;
-    int32_t reserved;
+    int32_t applied;   /* != 0: updated upstream, skipped (slab NULL, splits 0) */
 } fh_grad_slab;
 int fh_sgd_step_slabs(float* param, float* grad, float* momentum_buf, int64_t row_stride,
                       int64_t row_len, int32_t nclients, const fh_grad_slab* slabs,
@@ -504,6 +508,52 @@ int fh_linear_bwd_fused_pool(const float* x, int64_t x_cs, const float* dy, int6
                              int64_t pi_cs, const int32_t* counts, int32_t nclients, int32_t batch,
                              int32_t C, int32_t OH, int32_t OW, int32_t xh, int32_t xw,
                              int32_t out_f, void* stream);
+
+/*
+ * The fused linear backward with the optimizer update applied where the weight gradient is
+ * produced (fh_linear_bwd_fused_upd, fh_linear_bwd_fused_pool_upd).  When the update is fused,
+ * the layer's DGRAD is launched first (it reads the weights) and the WGRAD launch then applies
+ * fh_sgd_step's / fh_adam_step's update to the layer's weight and bias elements instead of
+ * storing dw / db: same gradient bits, same update operations, so parameters and state equal
+ * the unfused call followed by fh_sgd_step_slabs / fh_adam_step_slabs bit for bit; dw and db
+ * are then left untouched and the optimizer launch must skip their ranges (fh_grad_slab.applied).
+ * *applied (required) says which happened: 1 = the update is applied, 0 = the launch was
+ * fh_linear_bwd_fused's own (dw / db written, parameters untouched).
+ *   mode 1: fuse only at the widths where the backward already runs as two launches;
+ *   mode 2: fuse at every width (two launches where one dual-role launch ran before).
+ * pw / pb: the layer's weight / bias in the parameter rows (pw is normally w itself); s1* / s2*:
+ * the same elements of the optimizer state rows, at the parameters' client strides (s1 NULL
+ * for SGD without momentum, s2 used by Adam only).  The scalars are those of fh_sgd_step
+ * (adam == 0: lr, momentum, weight_decay, first_step) or fh_adam_step (adam != 0), scal_dev
+ * included.  pb and the bias states may be NULL when db is NULL.
+ */
+typedef struct {
+    float* pw;
+    int64_t pw_cs;
+    float* pb;
+    int64_t pb_cs;
+    float* s1w;
+    float* s1b;
+    float* s2w;
+    float* s2b;
+    int32_t adam, decoupled, first_step, mode;
+    double lr, momentum, weight_decay, beta1, beta2, eps, step_size, bc2_sqrt;
+    const float* scal_dev;
+} fh_linear_update;
+int fh_linear_bwd_fused_upd(const float* x, int64_t x_cs, const float* dy, int64_t dy_cs,
+                            const float* w, int64_t w_cs, float* dw, int64_t dw_cs, float* db,
+                            int64_t db_cs, float* dx, int64_t dx_cs, const uint8_t* mask,
+                            int64_t m_cs, float p_drop, const float* relu_ref, int64_t r_cs,
+                            const int32_t* counts, int32_t nclients, int32_t batch,
+                            int32_t in_f, int32_t out_f, const fh_linear_update* upd,
+                            int32_t* applied, void* stream);
+int fh_linear_bwd_fused_pool_upd(const float* x, int64_t x_cs, const float* dy, int64_t dy_cs,
+                                 const float* w, int64_t w_cs, float* dw, int64_t dw_cs,
+                                 float* db, int64_t db_cs, float* dx, int64_t dx_cs,
+                                 const uint8_t* pidx, int64_t pi_cs, const int32_t* counts,
+                                 int32_t nclients, int32_t batch, int32_t C, int32_t OH,
+                                 int32_t OW, int32_t xh, int32_t xw, int32_t out_f,
+                                 const fh_linear_update* upd, int32_t* applied, void* stream);
 
 /* ---------------- BatchNorm2d (+ReLU, +residual add) ----------------------
  * x/y/res: [clients][batch][C][HW]; gamma/beta live in the per-client param
