@@ -209,6 +209,12 @@ SIGNATURES = {
     "fh_sparse_validate": (I32, [P, I64, I32, P, P, I32, P, P]),
     "fh_sparse_unpack_rows": (I32, [P, I64, P, I64, P, I64, P, I64, I32, P, P, P, I32, I32, P]),
     "fh_sparse_fedavg": (I32, [P, I64, P, I64, P, P, I32, P, P, P, P, I32, I32, P, I32, P]),
+    "fh_quant_pack_rows": (I32, [P, I64, P, P, I64, P, I64, P, I64, P, I32, P, P, P, I32, I32, I32,
+                                 P]),
+    "fh_quant_validate": (I32, [P, I64, P, P, P, I32, P, P, I32, I32, P, P]),
+    "fh_quant_unpack_rows": (I32, [P, I64, P, P, P, P, I64, P, I64, I32, P, P, P, I32, I32, I32,
+                                   P]),
+    "fh_quant_fedavg": (I32, [P, I64, P, P, P, P, P, I32, P, P, P, P, I32, I32, I32, P, I32, P]),
     "fh_eval_metrics": (I32, [P, I64, P, I64, P, I32, I32, I32, P, P, P, P, P]),
     "fh_avgpool_fwd": (I32, [P, I64, P, I64, P, I32, I32, I32, I32, P]),
     "fh_avgpool_bwd": (I32, [P, I64, P, I64, P, I32, I32, I32, I32, P]),

@@ -37,7 +37,9 @@ class CompressionConfig:
     ("quantization" only, bits >= 2): unbiased stochastic rounding instead of the reference's
     round-half-to-even.  sparse ("topk" only): a round also keeps every client's update as
     the packed (index, value) payload of fedhip/sparse.py and aggregates from it where it can
-    (DESIGN.md D21); the global model is the same, bit for bit.  All are off by default: the
+    (DESIGN.md D21); the global model is the same, bit for bit.  packed ("quantization" only,
+    bits <= 8, not stochastic): the same for the quantiser, with the bit-packed codes of
+    fedhip/quantpack.py as the payload.  All are off by default: the
     reference's compressors, bit for bit."""
     algorithm: str = "topk"
     sparsity_ratio: float = 0.9
@@ -46,6 +48,7 @@ class CompressionConfig:
     error_feedback: bool = False
     stochastic: bool = False
     sparse: bool = False
+    packed: bool = False
 
     def __post_init__(self):
         if self.algorithm not in ("quantization", "topk"):
@@ -58,6 +61,16 @@ class CompressionConfig:
         if self.sparse and self.algorithm != "topk":
             raise FedHipError("sparse payloads are an option of algorithm='topk' "
                               f"(got {self.algorithm!r})")
+        if self.packed:
+            if self.algorithm != "quantization":
+                raise FedHipError("packed payloads are an option of algorithm='quantization' "
+                                  f"(got {self.algorithm!r})")
+            if self.stochastic:
+                raise FedHipError("packed payloads carry the deterministic quantiser's header: "
+                                  "stochastic=True is not supported with packed=True")
+            if not 1 <= self.bits <= 8:
+                raise FedHipError("packed payloads hold uint8 codes: bits must be in [1, 8] "
+                                  f"(got {self.bits})")
 
 
 def topk_k(numel: int, sparsity_ratio: float) -> int:
@@ -177,8 +190,8 @@ _KEEP: dict = {}
 
 
 def _keep_scratch(like, nclients):
-    """uint8 keep mask [nclients, row stride of `like`] for the error-feedback top-k, one per
-    (device, stream), grow-only."""
+    """uint8 scratch [nclients, row stride of `like`], one per (device, stream), grow-only:
+    the top-k keep mask, or the quantiser's one-byte codes on their way to a packed payload."""
     k = (str(like.device), torch.cuda.current_stream(like.device).cuda_stream)
     n, w = nclients, like.stride(0)
     t = _KEEP.get(k)
@@ -191,7 +204,7 @@ def compress_rows(plan: SegmentPlan, cfg: CompressionConfig, rows, nclients,
                   base: Optional[torch.Tensor] = None, resid: Optional[torch.Tensor] = None,
                   key: Optional[int] = None, row_ids: Optional[torch.Tensor] = None,
                   words: Optional[torch.Tensor] = None, sparse_out=None,
-                  rewrite_rows: bool = True):
+                  rewrite_rows: bool = True, quant_out=None):
     """In place: rows[:nclients] <- base + decompress(compress(rows - base)).
 
     cfg.error_feedback: the update compressed is v = (rows - base) + resid and resid
@@ -201,7 +214,23 @@ def compress_rows(plan: SegmentPlan, cfg: CompressionConfig, rows, nclients,
     sparse_out (a fedhip.sparse.SparseUpdates of this plan at cfg.sparsity_ratio, "topk" only)
     also receives the kept (index, value) pairs of every client.  rewrite_rows=False (with
     sparse_out, without error feedback) then leaves rows as they came: the payload is the
-    update."""
+    update.
+    quant_out (a fedhip.quantpack.QuantUpdates of this plan at cfg.bits, the deterministic
+    "quantization" with bits <= 8 only) receives every client's packed codes, scale, zero point
+    and pass-through value in the same way; rewrite_rows=False works as with sparse_out."""
+    if quant_out is not None:
+        if cfg.algorithm != "quantization":
+            raise FedHipError("quant_out= needs algorithm='quantization'")
+        if cfg.stochastic:
+            raise FedHipError("quant_out= carries the deterministic quantiser's header: "
+                              "stochastic=True is not supported")
+        if not 1 <= cfg.bits <= 8:
+            raise FedHipError(f"quant_out= holds uint8 codes: bits must be in [1, 8] "
+                              f"(got {cfg.bits})")
+        if quant_out.plan.plan is not plan or quant_out.plan.bits != int(cfg.bits):
+            raise FedHipError("quant_out= was laid out for another segment plan or bit width")
+        from .quantpack import quant_pack_rows, quant_unpack_rows
+        quant_out.symmetric = bool(cfg.symmetric)
     if sparse_out is not None:
         if cfg.algorithm != "topk" or cfg.stochastic:
             raise FedHipError("sparse_out= needs algorithm='topk'")
@@ -233,6 +262,15 @@ def compress_rows(plan: SegmentPlan, cfg: CompressionConfig, rows, nclients,
             return rows
         if cfg.algorithm == "topk":
             return topk_rows(plan, rows, nclients, cfg.sparsity_ratio, base=base, out=rows)
+        if quant_out is not None:
+            # the pack reads x - base of a passed-through segment: the rows are rewritten last
+            codes = _keep_scratch(rows, nclients)
+            quantize_rows(plan, rows, nclients, cfg.bits, cfg.symmetric, base=base, codes=codes,
+                          scale_out=quant_out.scale, zp_out=quant_out.zp)
+            quant_pack_rows(quant_out, rows, codes, nclients, base=base)
+            if rewrite_rows:
+                quant_unpack_rows(quant_out, rows, nclients, base=base)
+            return rows
         return quantize_rows(plan, rows, nclients, cfg.bits, cfg.symmetric, base=base, out=rows)
     ef_fold(plan, rows, resid, nclients, base=base)
     if cfg.algorithm == "topk":
@@ -242,5 +280,11 @@ def compress_rows(plan: SegmentPlan, cfg: CompressionConfig, rows, nclients,
             topk_pack_rows(sparse_out, resid, keep, nclients)
         return ef_topk_finish(plan, keep, resid, rows, nclients, base=base)
     # the rows are rewritten by the finish anyway: they hold c in between
+    if quant_out is not None:  # the pack before the finish: it turns resid from v into v - c
+        codes = _keep_scratch(rows, nclients)
+        quantize_rows(plan, resid, nclients, cfg.bits, cfg.symmetric, out=rows, codes=codes,
+                      scale_out=quant_out.scale, zp_out=quant_out.zp)
+        quant_pack_rows(quant_out, resid, codes, nclients)
+        return ef_quant_finish(plan, rows, resid, rows, nclients, base=base)
     quantize_rows(plan, resid, nclients, cfg.bits, cfg.symmetric, out=rows)
     return ef_quant_finish(plan, rows, resid, rows, nclients, base=base)

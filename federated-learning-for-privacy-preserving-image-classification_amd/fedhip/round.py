@@ -70,6 +70,16 @@ plain FedAvg routes (no ``aggregator``, no ``central_dp``, not ``exact``) sum fr
 leave the trained rows as they are; with ``server_opt`` on one rank the sum lands in ``partial``
 and ``step_vector`` follows.  The other routes rebuild the dense rows from the payload first.
 The global model, ``global_bufs`` and ``residual`` are bit for bit those of ``sparse=False``.
+
+``packed=True`` (deterministic quantisation with bits <= 8 only; fedhip/quantpack.py, DESIGN.md
+D22) is the quantiser's counterpart: every client's codes are bit-packed into payload rows next to
+their scale and zero point, kept as ``last_quant`` (one row per slot, rewritten by every
+``run()``; ``wire.quant_to_payloads`` turns it into the reference's upload dicts).  The plain
+FedAvg routes (no ``aggregator``, no ``central_dp``, not ``exact``; one or several ranks, with or
+without ``server_opt``) sum the parameter aggregate from the payload with ``quant_fedavg`` and
+leave the trained rows as they are; the other routes rebuild the dense rows first and proceed as
+without it.  ``global_flat``, ``global_bufs`` and ``residual`` are bit for bit those of
+``packed=False``.
 """
 from __future__ import annotations
 
@@ -225,6 +235,13 @@ class RankRound:
             from .sparse import SparsePlan
             self._sparse = SparsePlan(self._cplan, compression.sparsity_ratio).empty(
                 len(self.slots))
+        # packed quantised updates (D22): the slots' code rows, rewritten every round;
+        # last_quant is the payload of the last run()
+        self._quant = None
+        self.last_quant = None
+        if compression is not None and compression.packed:
+            from .quantpack import QuantPlan
+            self._quant = QuantPlan(self._cplan, compression.bits).empty(len(self.slots))
         self.exact = bool(exact) and self.distributed
         if self.exact:
             self._init_exact()
@@ -295,6 +312,11 @@ class RankRound:
         return self._sparse is not None and self.aggregator is None and self.central is None \
             and not self.exact
 
+    def _quant_sum(self):
+        """The same for the packed quantised payload."""
+        return self._quant is not None and self.aggregator is None and self.central is None \
+            and not self.exact
+
     def reset_compression_state(self):
         """Forget every client's error-feedback residual (a new training run, or a new
         client-to-slot assignment, on the same RankRound)."""
@@ -336,6 +358,9 @@ class RankRound:
                 # the plain FedAvg sums straight from the payload: the rows stay as trained
                 extra.update(sparse_out=self._sparse, rewrite_rows=not self._sparse_sum())
                 self.last_sparse = self._sparse
+            if self._quant is not None:
+                extra.update(quant_out=self._quant, rewrite_rows=not self._quant_sum())
+                self.last_quant = self._quant
             compress_rows(self._cplan, self.compression, tr.params, S,
                           base=self.global_flat.view(1, -1).expand(S, -1), **extra)
         distributed = self.distributed
@@ -379,13 +404,18 @@ class RankRound:
             if sopt is not None:
                 sopt.step_vector(self.partial, self.global_flat)
         elif self.aggregator is None:
-            if sopt is not None and not distributed and self._sparse is None:
+            if sopt is not None and not distributed and self._sparse is None \
+                    and self._quant is None:
                 sopt.step_rows(tr.params, self.w32, self.global_flat, self.rows)  # one launch
             else:
                 if self._sparse is not None:  # the same sum from the (index, value) payload
                     from .sparse import sparse_fedavg
                     sparse_fedavg(self._sparse, self.w32, self.global_flat, self.partial,
                                   row_index=self.rows)
+                elif self._quant is not None:  # ... and from the packed codes
+                    from .quantpack import quant_fedavg
+                    quant_fedavg(self._quant, self.w32, self.global_flat, self.partial,
+                                 row_index=self.rows)
                 else:
                     ops.fedavg_weighted_sum(tr.params, self.w32, self.partial,
                                             row_index=self.rows, P=self.P)

@@ -141,6 +141,128 @@ def payloads_to_sparse(payloads: Sequence[Dict], layout, plan, device):
     return upd
 
 
+# ------------------------------------------------------------------ quantised payloads
+def _codes_per_byte(raw, cw: int, n: int):
+    """numpy uint8 [n]: the first n codes of cw bits each in the bytes raw, low bits first."""
+    import numpy as np
+    if cw == 8:
+        return raw[:n].copy()
+    sh = (np.arange(8 // cw, dtype=np.uint8) * cw)[None, :]
+    return ((raw[:, None] >> sh) & np.uint8((1 << cw) - 1)).reshape(-1)[:n].copy()
+
+
+def _bytes_of_codes(codes, cw: int):
+    """The inverse: numpy uint8 [ceil(n * cw / 8)], unused high bits of the last byte zero."""
+    import numpy as np
+    if cw == 8:
+        return codes
+    per = 8 // cw
+    pad = np.zeros(-(-codes.size // per) * per, np.uint8)
+    pad[:codes.size] = codes
+    sh = (np.arange(per, dtype=np.uint8) * cw)[None, :]
+    return np.bitwise_or.reduce(pad.reshape(-1, per) << sh, axis=1).astype(np.uint8)
+
+
+def quant_to_payloads(updates, layout, nclients: int, symmetric: bool = None) -> List[Dict]:
+    """The clients' quantised uploads as QuantizationCompressor.compress builds them
+    (compression.py:138-172), from a device payload (fedhip.quantpack.QuantUpdates) with ONE
+    D2H copy.  Per client ``{'compressed_weights': {name: uint8 tensor of the layer's shape},
+    'metadata': {'algorithm', 'bits', 'symmetric', 'quantization_params': {name: {'scale',
+    'zero_point', 'original_shape', 'original_dtype'}}}}``, one code per byte.  A layer the
+    quantiser passed through (asymmetric mode on a constant layer: the reference raises there)
+    has no such form: FedHipError naming client and layer.  symmetric: the quantiser's mode for
+    the metadata; by default ``updates.symmetric``, which compress_rows and payloads_to_quant
+    record.  It is never guessed from the zero points: a payload of unknown mode is refused."""
+    from .quantpack import INT64_MIN
+    qp = updates.plan
+    B, nseg, n = qp.B, qp.plan.nseg, int(nclients)
+    dev = torch.cat([updates.codes[:n, :B].reshape(-1),
+                     updates.scale[:n].reshape(-1).view(torch.uint8),
+                     updates.zp[:n].reshape(-1).view(torch.uint8)]).to("cpu")
+    codes = dev[:n * B].view(n, B).numpy()
+    scale = dev[n * B:n * B + 8 * n * nseg].view(torch.float64).view(n, nseg).tolist()
+    zp = dev[n * B + 8 * n * nseg:].view(torch.int64).view(n, nseg).tolist()
+    if symmetric is None:
+        symmetric = updates.symmetric
+    if symmetric is None:
+        raise ops.FedHipError("quant_to_payloads: the quantiser's mode is not recorded in the "
+                              "payload (updates.symmetric is None): pass symmetric=")
+    out = []
+    for z in range(n):
+        cw, params = {}, {}
+        for s, (name, shape) in enumerate(zip(layout.names, layout.shapes)):
+            if zp[z][s] == INT64_MIN:
+                raise ops.FedHipError(f"client {z}: layer {name} is constant and was passed "
+                                      "through unquantised: the reference's upload format "
+                                      "cannot express it")
+            a = qp.boff_host[s]
+            flat = _codes_per_byte(codes[z, a:a + qp.seg_bytes[s]], qp.cw, qp.plan.lengths[s])
+            cw[name] = torch.from_numpy(flat).reshape(tuple(shape))
+            params[name] = {"scale": scale[z][s], "zero_point": zp[z][s],
+                            "original_shape": torch.Size(shape),
+                            "original_dtype": "torch.float32"}
+        out.append({"compressed_weights": cw,
+                    "metadata": {"algorithm": f"quantization_{qp.bits}bit", "bits": qp.bits,
+                                 "symmetric": bool(symmetric), "quantization_params": params}})
+    return out
+
+
+def payloads_to_quant(payloads: Sequence[Dict], layout, plan, device):
+    """Received quantised uploads -> validated device payload (one H2D copy).  payloads: per
+    client what quant_to_payloads returns, or a dict with ``compressed_weights`` and
+    ``quantization_params`` alone; plan: the fedhip.quantpack.QuantPlan of the layout and bit
+    width.  A missing layer, a wrong shape or dtype, a zero point no int64 holds, and whatever
+    fh_quant_validate flags (a code >= 2^bits, a scale that is not finite or negative) raise
+    FedHipError naming client and layer before any consumer sees the payload."""
+    import numpy as np
+    from .quantpack import INT64_MIN, QuantUpdates, quant_validate
+    B, nseg, C = plan.B, plan.plan.nseg, len(payloads)
+    n = max(C, 1)
+    host = np.zeros(n * B + 20 * n * nseg, np.uint8)
+    codes = host[:n * B].reshape(n, B)
+    scale = host[n * B:n * B + 8 * n * nseg].view(np.float64).reshape(n, nseg)
+    zp = host[n * B + 8 * n * nseg:n * B + 16 * n * nseg].view(np.int64).reshape(n, nseg)
+    modes = set()
+    for z, p in enumerate(payloads):
+        cw = p["compressed_weights"]
+        params = p["metadata"]["quantization_params"] if "metadata" in p \
+            else p["quantization_params"]
+        modes.add(p.get("metadata", {}).get("symmetric"))
+        for s, (name, shape) in enumerate(zip(layout.names, layout.shapes)):
+            if name not in cw or name not in params:
+                raise ops.FedHipError(f"client {z}: layer {name} is missing from the payload")
+            t = cw[name]
+            if t.dtype != torch.uint8:
+                raise ops.FedHipError(f"client {z}: layer {name} has dtype {t.dtype}, expected "
+                                      "torch.uint8")
+            if tuple(t.shape) != tuple(shape):
+                raise ops.FedHipError(f"client {z}: layer {name} has shape {tuple(t.shape)}, "
+                                      f"expected {tuple(shape)}")
+            zero = int(params[name]["zero_point"])
+            if not INT64_MIN < zero < 2 ** 63:
+                raise ops.FedHipError(f"client {z}: layer {name} has a zero point no int64 holds")
+            flat = t.reshape(-1).cpu().numpy()
+            if plan.cw < 8 and int(flat.max()) >> plan.cw:  # would not survive the packing
+                raise ops.FedHipError(f"client {z}: layer {name} has a code >= 2^{plan.bits}")
+            a = plan.boff_host[s]
+            codes[z, a:a + plan.seg_bytes[s]] = _bytes_of_codes(flat, plan.cw)
+            scale[z, s] = float(params[name]["scale"])
+            zp[z, s] = zero
+    dev = torch.from_numpy(host).to(device)
+    f64 = dev[n * B:n * B + 8 * n * nseg].view(torch.float64).view(n, nseg)
+    i64 = dev[n * B + 8 * n * nseg:n * B + 16 * n * nseg].view(torch.int64).view(n, nseg)
+    f32 = dev[n * B + 16 * n * nseg:].view(torch.float32).view(n, nseg)
+    mode = modes.pop() if len(modes) == 1 else None   # what every client's metadata states
+    upd = QuantUpdates(dev[:n * B].view(n, B)[:C], f64[:C], i64[:C], f32[:C], plan,
+                       None if mode is None else bool(mode))
+    bad = quant_validate(upd).to("cpu")
+    if bool(bad.any()):
+        z, s = [int(t) for t in bad.nonzero()[0]]
+        raise ops.FedHipError(f"client {z}: layer {layout.names[s]} has a code >= "
+                              f"2^{plan.bits}, or a scale that is not finite or negative")
+    return upd
+
+
 def weight_change_metrics(current: torch.Tensor, previous: torch.Tensor,
                           seg_offsets: torch.Tensor) -> Dict[str, float]:
     """{'norm': ||current - previous||, 'relative': norm / ||current||} over the layers

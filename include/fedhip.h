@@ -39,6 +39,10 @@
  *   fh_topk_pack_rows / fh_sparse_validate / fh_sparse_unpack_rows / fh_sparse_fedavg
  *                            TopKSparsificationCompressor's {'values', 'indices'} payload
  *                            (compression.py:262-297, 346-365) and FedAvg straight from it
+ *   fh_quant_pack_rows / fh_quant_validate / fh_quant_unpack_rows / fh_quant_fedavg
+ *                            QuantizationCompressor's uint8 codes + quantization_params payload
+ *                            (compression.py:138-172, 230-244), bit-packed, and FedAvg straight
+ *                            from it
  */
 #ifndef FEDHIP_H_
 #define FEDHIP_H_
@@ -1212,6 +1216,85 @@ int fh_sparse_fedavg(const int32_t* idx, int64_t idx_cs, const float* val, int64
                      const float* base, const int64_t* seg_offsets, const int32_t* chunk_offsets,
                      const int32_t* koff, int32_t nseg, int32_t nchunks, float* out,
                      int32_t accumulate, void* stream);
+
+/* ---------------- packed quantised updates (compression.py:138-244) -----
+ * What QuantizationCompressor ships per layer, a uint8 code per element plus {scale, zero_point},
+ * as bit-packed code rows, and the aggregation from it.  The deterministic quantiser
+ * (fh_quantize_rows) with bits in [1, 8] only.  Conventions of the blocks above: device pointers
+ * with element strides, base nullable (base_cs 0 broadcasts one row), segments by seg_offsets /
+ * chunk_offsets, nothing outside [seg_offsets[0], seg_offsets[nseg]) of a parameter row is read or
+ * written, one launch for all clients, no atomics, no host sync.  fl32() marks one rounded fp32
+ * operation; none is ever fused.
+ *
+ * Payload.  A code occupies cw bits: cw = 1 for bits 1, 2 for bits 2, 4 for bits 3..4, 8 for bits
+ * 5..8.  Element j (segment-local) of segment s sits in byte boff[s] + (j * cw) / 8 of a client's
+ * code row, at bits [(j * cw) % 8, (j * cw) % 8 + cw), low bits first.  boff (device
+ * int64[nseg+1]) is the exclusive prefix sum of ceil(len_s * cw / 8) rounded up to 16; B =
+ * boff[nseg].  Code rows must be 16-byte aligned with a row stride (bytes) that is a multiple of
+ * 16, else FH_E_INVALID: every load of codes is an aligned vector load.  Nothing outside a
+ * segment's ceil(len_s * cw / 8) bytes of a code row is read or written (the padding up to the
+ * next 16-byte boundary included).  fp32 parameter rows keep their usual freedom: any 4-byte
+ * alignment, any stride, segments starting anywhere.
+ * Next to the codes, [nclients][nseg] each and contiguous: scale (double) and zp (int64) exactly
+ * as fh_quantize_rows writes scale_out / zp_out, and passv (fp32).
+ *
+ * Dequantisation (quant_apply_kernel's arithmetic):
+ *     d = fl32( fl32( (float)code - (float)zp ) * (float)scale )
+ * An all-zero symmetric segment has code 0 and d = -0.0 ((0 - 127) * 0): no special case.
+ * Pass-through.  zp == INT64_MIN marks a segment fh_quantize_rows passed through (asymmetric mode
+ * on a constant segment).  With finite input its v are numerically equal and differ at most in
+ * the sign of zero: the payload carries passv = v of the segment's first element and code = sign
+ * bit of v per element, and d = the magnitude bits of passv under bit 0 of the code as sign.
+ * Non-finite input: unspecified, as for fh_quantize_rows.
+ *
+ * fh_quant_pack_rows    codes: the uint8 rows fh_quantize_rows wrote (one code per element,
+ *                       indexed like x, stride codes_cs); zp: its zp_out; x / base: the same as
+ *                       in that call.  Writes packed (the code rows) and passv.  One thread
+ *                       assembles whole bytes; the unused high bits of a segment's last byte are
+ *                       written as zero, the padding bytes are not written.  A flagged segment
+ *                       reads v = fl32(x[z][i] - base[z][i]) (base NULL: x[z][i]) instead of the
+ *                       codes; passv of an unflagged segment is written as +0.0.
+ * fh_quant_validate     bad_out[z][s] (int32 [nclients][nseg]) = 1 when segment s of client z
+ *                       holds a code >= 2^bits (possible only where bits < cw), when scale is not
+ *                       finite or is negative, or when the segment is flagged and passv is not
+ *                       finite; else 0.  seg_lens: device int64[nseg].  Padding bits and bytes
+ *                       are not looked at.  The two consumers below take VALIDATED payloads only;
+ *                       on any other payload their result is unspecified (they still write
+ *                       nothing outside the rows' covered range).
+ * fh_quant_unpack_rows  out[z][i] = fl32(base[z][i] + d[z][i])   (base NULL: d[z][i]) — that is
+ *                       fh_quantize_rows' own out.  out may alias base only when base_cs != 0.
+ * fh_quant_fedavg       base is ONE row (the global model) or NULL, out one row, neither aliasing
+ *                       the other.  For every j of the covered range
+ *                         acc = accumulate ? out[j] : +0.0
+ *                         for k = 0 .. num_clients-1, r = row_index[k] (NULL: k):
+ *                           xk  = fl32(base[j] + d[r][j])        (base NULL: d[r][j])
+ *                           acc = fl32(acc + fl32(weights[k] * xk))
+ *                         out[j] = acc
+ *                       — bit for bit fh_fedavg_weighted_sum over the rows fh_quant_unpack_rows
+ *                       (base broadcast) would write, without them.
+ *                       Bytes moved: cw / 8 per element and client, 8 per parameter. */
+int fh_quant_pack_rows(const uint8_t* codes, int64_t codes_cs, const int64_t* zp, const float* x,
+                       int64_t x_cs, const float* base, int64_t base_cs, uint8_t* packed,
+                       int64_t packed_cs, float* passv, int32_t nclients,
+                       const int64_t* seg_offsets, const int32_t* chunk_offsets,
+                       const int64_t* boff, int32_t nseg, int32_t nchunks, int32_t bits,
+                       void* stream);
+int fh_quant_validate(const uint8_t* packed, int64_t packed_cs, const double* scale,
+                      const int64_t* zp, const float* passv, int32_t nclients,
+                      const int64_t* seg_lens, const int64_t* boff, int32_t nseg, int32_t bits,
+                      int32_t* bad_out, void* stream);
+int fh_quant_unpack_rows(const uint8_t* packed, int64_t packed_cs, const double* scale,
+                         const int64_t* zp, const float* passv, const float* base,
+                         int64_t base_cs, float* out, int64_t out_cs, int32_t nclients,
+                         const int64_t* seg_offsets, const int32_t* chunk_offsets,
+                         const int64_t* boff, int32_t nseg, int32_t nchunks, int32_t bits,
+                         void* stream);
+int fh_quant_fedavg(const uint8_t* packed, int64_t packed_cs, const double* scale,
+                    const int64_t* zp, const float* passv, const int32_t* row_index,
+                    const float* weights, int32_t num_clients, const float* base,
+                    const int64_t* seg_offsets, const int32_t* chunk_offsets, const int64_t* boff,
+                    int32_t nseg, int32_t nchunks, int32_t bits, float* out, int32_t accumulate,
+                    void* stream);
 
 /* ---------------- evaluation metrics (training.py:214-242, 307-360) ----------
  * Eval-mode metrics of [nclients][batch][K] logits: per image the first-index
