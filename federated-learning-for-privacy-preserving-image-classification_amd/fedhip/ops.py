@@ -10,6 +10,7 @@ the arithmetic is the kernels'.
 from __future__ import annotations
 
 import ctypes
+import math
 import os
 from dataclasses import dataclass
 
@@ -1250,6 +1251,115 @@ def server_opt_step(rows, global_, m, v, rule, server_lr, beta1, beta2, tau, wei
          ptr(global_), ptr(m), ptr(v), int(rule), float(server_lr), float(beta1), float(beta2),
          float(tau), stream_handle())
     return global_
+
+
+# ------------------------------------------------------------------ FedNova
+NOVA_STEP, NOVA_PARTIAL, NOVA_FINISH = range(3)  # FH_NOVA_* of include/fedhip.h
+
+
+def fednova_coefficients(weights, local_steps, tau_eff="weighted"):
+    """Host side of FedNova (Wang et al., NeurIPS 2020): from the FedAvg weights p_k and the
+    local step counts a_k, the per-client coefficients c_k = p_k / a_k and
+    tau_eff = sum_k p_k * a_k, both in Python double (a plain sum in the given order); the
+    caller's float32 tensor / argument conversion rounds them to fp32.  An explicit finite
+    positive `tau_eff` replaces the weighted one.  A client with a_k == 0 (an empty shard)
+    must have p_k == 0: its coefficient is 0 and it adds nothing to tau_eff.  Returns
+    (coef: list[float], tau_eff: float); ValueError for anything else."""
+    p = [float(w) for w in weights]
+    steps = list(local_steps)
+    if len(p) != len(steps):
+        raise ValueError(f"fednova: {len(p)} weights for {len(steps)} local step counts")
+    a = []
+    for s in steps:
+        if isinstance(s, bool) or int(s) != s:
+            raise ValueError(f"fednova: local step counts must be integers: {s!r}")
+        if int(s) < 0:
+            raise ValueError(f"fednova: negative local step count {s!r}")
+        a.append(int(s))
+    coef, tau = [], 0.0
+    for pk, ak in zip(p, a):
+        if not math.isfinite(pk):
+            raise ValueError(f"fednova: non-finite weight {pk!r}")
+        if ak == 0:
+            if pk != 0.0:
+                raise ValueError("fednova: a client with no local step must have weight 0 "
+                                 f"(got {pk!r})")
+            coef.append(0.0)
+            continue
+        coef.append(pk / ak)
+        tau = tau + pk * ak
+    if isinstance(tau_eff, str):
+        if tau_eff != "weighted":
+            raise ValueError(f"fednova: tau_eff must be 'weighted' or a finite positive "
+                             f"number: {tau_eff!r}")
+    else:
+        if isinstance(tau_eff, bool) or not isinstance(tau_eff, (int, float)) \
+                or not math.isfinite(tau_eff) or tau_eff <= 0:
+            raise ValueError(f"fednova: tau_eff must be 'weighted' or a finite positive "
+                             f"number: {tau_eff!r}")
+        tau = float(tau_eff)
+    return coef, tau
+
+
+def fednova_rows(rows, coef_f32, global_, out, tau_eff, mode, row_index=None, P=None):
+    """One FedNova launch (the arithmetic is defined in include/fedhip.h), with
+    acc = sum_k coef_k * (rows[row_index[k]] - global_) summed sequentially in fp32:
+      NOVA_STEP     out = global_ + tau_eff * acc
+      NOVA_PARTIAL  out = acc                         (a rank's share, to all-reduce)
+      NOVA_FINISH   out = global_ + tau_eff * rows[0]  (rows holds the ONE all-reduced sum;
+                                                        coef_f32 is None)
+    global_ and out are contiguous fp32 [>= P]; out may be global_ in STEP and FINISH and
+    rows' own storage in FINISH.  Returns out."""
+    require_device(rows, "rows")
+    for t, what in ((global_, "global_"), (out, "out"), (coef_f32, "coef_f32"),
+                    (row_index, "row_index")):
+        if t is not None:
+            require_device(t, what)
+    if global_ is None or out is None:
+        raise FedHipError("fednova: global_ and out are required")
+    mode = int(mode)
+    if mode not in (NOVA_STEP, NOVA_PARTIAL, NOVA_FINISH):
+        raise FedHipError(f"fednova: mode={mode} outside [0, 2]")
+    if rows.dim() != 2:
+        raise FedHipError(f"fednova: rows must be a float32 [clients, >= P] matrix (got shape "
+                          f"{tuple(rows.shape)})")
+    if row_index is not None and (row_index.dtype != torch.int32
+                                  or not row_index.is_contiguous()):
+        raise FedHipError("fednova: row_index must be a contiguous int32 vector")
+    if mode == NOVA_FINISH:
+        if coef_f32 is not None:
+            raise FedHipError("fednova: FINISH takes the all-reduced sum, not coefficients")
+        C = rows.shape[0] if row_index is None else row_index.numel()
+        if C != 1:
+            raise FedHipError(f"fednova: FINISH takes ONE row, the all-reduced sum (got {C})")
+    else:
+        if coef_f32 is None:
+            raise FedHipError("fednova: coef_f32 is required outside FINISH")
+        if coef_f32.dtype != torch.float32 or not coef_f32.is_contiguous():
+            raise FedHipError("fednova: coef_f32 must be a contiguous float32 vector")
+        C = coef_f32.numel()
+        if C < 1:
+            raise FedHipError("fednova: no client")
+        if row_index is not None and row_index.numel() != C:
+            raise FedHipError(f"fednova: {row_index.numel()} row indices for {C} coefficients")
+        if row_index is None and rows.shape[0] < C:
+            raise FedHipError(f"fednova: {rows.shape[0]} rows for {C} coefficients and no "
+                              f"row_index")
+    P = rows.shape[1] if P is None else int(P)
+    if rows.dtype != torch.float32 or P < 0 or P > rows.shape[1] \
+            or (P and rows.stride(1) != 1):
+        raise FedHipError(f"fednova: rows must be float32 with unit column stride and at "
+                          f"least P={P} columns (got {rows.dtype} {tuple(rows.shape)})")
+    for t, what in ((global_, "global_"), (out, "out")):
+        if t.dtype != torch.float32 or not t.is_contiguous() or t.numel() < P:
+            raise FedHipError(f"fednova: {what} must be a contiguous float32 vector of at "
+                              f"least P={P} elements (got {t.dtype} {tuple(t.shape)})")
+    tau_eff = float(tau_eff)
+    if mode != NOVA_PARTIAL and not math.isfinite(ctypes.c_float(tau_eff).value):
+        raise FedHipError(f"fednova: tau_eff={tau_eff!r} is not finite in fp32")
+    call("fh_fednova_rows", ptr(rows), rows.stride(0), ptr(row_index), ptr(coef_f32), C, P,
+         ptr(global_), tau_eff, mode, ptr(out), stream_handle())
+    return out
 
 
 # ------------------------------------------------------------------ central DP-FedAvg

@@ -80,6 +80,22 @@ without ``server_opt``) sum the parameter aggregate from the payload with ``quan
 leave the trained rows as they are; the other routes rebuild the dense rows first and proceed as
 without it.  ``global_flat``, ``global_bufs`` and ``residual`` are bit for bit those of
 ``packed=False``.
+
+``fednova`` (``True`` or a src.aggregation.fednova.FedNovaConfig) replaces the FedAvg of the
+PARAMETER rows by FedNova's normalised average (Wang et al., NeurIPS 2020)
+    x_new = g + tau_eff * sum_k (p_k / a_k) * (x_k - g),      tau_eff = sum_k p_k * a_k,
+with a_k = epochs * ceil(n_k / batch) the local step count of client k.  The host knows every
+client's step count on every rank, so the coefficients and tau_eff are computed over all clients
+in global client order at construction and every rank holds the same tau_eff with no extra
+collective.  One rank: one STEP launch.  Several ranks: each rank's PARTIAL sum over its rows,
+the one all-reduce, then FINISH on every rank.  ``exact=True``: STEP over the all-gathered rows
+in global client order.  The result lands where FedAvg's would, so ``server_opt`` composes
+unchanged (a single-row step follows).  ``dp`` and ``compression`` stay allowed; the sums from the
+sparse and packed payloads are FedAvg's, so under FedNova the dense rows are rebuilt.  Refused
+with a robust ``aggregator`` (the rule is a weighted sum, the robust rules are not) and with
+``central_dp`` (its sensitivity argument needs uniform weights, D19).  The BN running statistics
+keep the plain FedAvg: they are not the product of gradient steps.  With ``fednova=None`` nothing
+changes.
 """
 from __future__ import annotations
 
@@ -111,7 +127,7 @@ class RankRound:
                  epochs: int = 1, batch: int = 32, device="cuda", dp: Optional[DPConfig] = None,
                  group=None, lanes=None, compression=None, transform=None, dp_seed=None,
                  shuffle_seed=None, exact=False, aggregator=None, server_opt=None,
-                 central_dp=None):
+                 central_dp=None, fednova=None):
         self.device = torch.device(device)
         self._template = template_model
         self.B, self.epochs, self.dp, self.group = batch, epochs, dp, group
@@ -133,6 +149,20 @@ class RankRound:
                 and dist.get_world_size(group) > 1:
             raise ops.FedHipError("a robust aggregator over several ranks needs exact=True: "
                                   "the rule is not a sum and cannot be all-reduced")
+        if fednova is not None and fednova is not False:
+            if fednova is True:
+                from src.aggregation.fednova import FedNovaConfig
+                fednova = FedNovaConfig()
+            if aggregator is not None:
+                raise ops.FedHipError("fednova is a weighted sum of normalised deltas and a "
+                                      "robust aggregator is not a sum: they cannot be combined")
+            if central_dp is not None:
+                raise ops.FedHipError("fednova weighs the clients by p_k / a_k and central_dp's "
+                                      "sensitivity argument needs uniform weights (D19): they "
+                                      "cannot be combined")
+        else:
+            fednova = None
+        self.fednova = fednova
         self.central = None
         if central_dp is not None:
             if dp is not None:
@@ -168,6 +198,18 @@ class RankRound:
                                 device=self.device)
         self.rows = torch.tensor([self.slot_of[k] for k in self.clients], dtype=torch.int32,
                                  device=self.device)
+        # FedNova: c_k = p_k / a_k and tau_eff over ALL clients in global client order (host
+        # double), the same on every rank; this rank's coefficients in client-list order
+        self._nova_coef = self._nova_c32 = self._nova_tau = None
+        if fednova is not None:
+            local_steps = [epochs * math.ceil(n / batch) for n in self.all_sizes]
+            try:
+                self._nova_coef, self._nova_tau = ops.fednova_coefficients(
+                    self.weights, local_steps, fednova.tau_eff)
+            except ValueError as e:
+                raise ops.FedHipError(f"fednova: {e}") from e
+            self._nova_c32 = torch.tensor([self._nova_coef[k] for k in self.clients],
+                                          dtype=torch.float32, device=self.device)
         # what a robust aggregator is handed on one rank: its clients' rows and sample counts
         self._agg_rows = [self.slot_of[k] for k in self.clients]
         self._agg_samples = [processed[k] for k in self.clients]
@@ -268,6 +310,9 @@ class RankRound:
         self._x_w32 = torch.tensor([self.weights[k] for k in order], dtype=torch.float32,
                                    device=self.device)
         self._x_idx = torch.tensor([pos[k] for k in order], dtype=torch.int32, device=self.device)
+        if self._nova_coef is not None:
+            self._x_c32 = torch.tensor([self._nova_coef[k] for k in order], dtype=torch.float32,
+                                       device=self.device)
         self._x_rows = [pos[k] for k in order]
         self._x_samples = [self.epochs * self.all_sizes[k] for k in order]
         self._x_mine = torch.tensor([self.slot_of[k] for k in self.clients], dtype=torch.int64,
@@ -308,14 +353,14 @@ class RankRound:
 
     def _sparse_sum(self):
         """Whether this round's parameter aggregate is summed from the sparse payload: the plain
-        FedAvg routes.  Exact mode, a robust rule and central DP read dense rows."""
+        FedAvg routes.  Exact mode, a robust rule, central DP and FedNova read dense rows."""
         return self._sparse is not None and self.aggregator is None and self.central is None \
-            and not self.exact
+            and not self.exact and self.fednova is None
 
     def _quant_sum(self):
         """The same for the packed quantised payload."""
         return self._quant is not None and self.aggregator is None and self.central is None \
-            and not self.exact
+            and not self.exact and self.fednova is None
 
     def reset_compression_state(self):
         """Forget every client's error-feedback residual (a new training run, or a new
@@ -375,6 +420,10 @@ class RankRound:
                 cdp.step_rows(self._exact_gather(tr.params, self.P), self.global_flat,
                               self._x_idx, m_all, self._round_key(seed), out=agg_out,
                               noise=self.central_noise)
+            elif self.fednova is not None:  # one STEP over every client's row, global order
+                ops.fednova_rows(self._exact_gather(tr.params, self.P), self._x_c32,
+                                 self.global_flat, agg_out, self._nova_tau, ops.NOVA_STEP,
+                                 row_index=self._x_idx, P=self.P)
             elif self.aggregator is None:
                 self._exact_fedavg(tr.params, self.P, agg_out)
             else:  # the rule over every client's row, in global client order, on every rank
@@ -401,6 +450,22 @@ class RankRound:
                 dist.all_reduce(bit_sum, op=dist.ReduceOp.SUM, group=self.group)
                 cdp.finish(part, bit_sum, self.global_flat, m_all, key, out=agg_out,
                            noise=self.central_noise)
+            if sopt is not None:
+                sopt.step_vector(self.partial, self.global_flat)
+        elif self.fednova is not None:
+            if not distributed:  # one launch: the whole rule over this rank's rows
+                ops.fednova_rows(tr.params, self._nova_c32, self.global_flat, agg_out,
+                                 self._nova_tau, ops.NOVA_STEP, row_index=self.rows, P=self.P)
+            else:  # this rank's share of the normalised sum, one all-reduce, every rank finishes
+                if self.clients:
+                    ops.fednova_rows(tr.params, self._nova_c32, self.global_flat, self.partial,
+                                     self._nova_tau, ops.NOVA_PARTIAL, row_index=self.rows,
+                                     P=self.P)
+                else:
+                    self.partial.zero_()
+                dist.all_reduce(self.partial, op=dist.ReduceOp.SUM, group=self.group)
+                ops.fednova_rows(self.partial.view(1, -1), None, self.global_flat, agg_out,
+                                 self._nova_tau, ops.NOVA_FINISH, P=self.P)
             if sopt is not None:
                 sopt.step_vector(self.partial, self.global_flat)
         elif self.aggregator is None:

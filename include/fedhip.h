@@ -183,6 +183,41 @@ int fh_server_opt_step(const float* rows, int64_t row_stride, const int32_t* row
                        float* global, float* m, float* v, int32_t rule,
                        float server_lr, float beta1, float beta2, float tau, void* stream);
 
+/* ---------------- FedNova normalised averaging (no reference counterpart) --
+ * Wang et al., "Tackling the Objective Inconsistency Problem in Heterogeneous Federated
+ * Optimization" (NeurIPS 2020): with FedAvg weights p_k and local step counts a_k the server sets
+ *     x_new = g + tau_eff * sum_k (p_k / a_k) * (x_k - g),        tau_eff = sum_k p_k * a_k,
+ * which is FedAvg when all a_k are equal.  The host passes coef[k] = fl32(p_k / a_k) (device
+ * float[num_clients]) and tau_eff.  Per coordinate j; every operation is one rounded fp32
+ * operation, never fused; denormals are kept:
+ *     g   = global[j]
+ *     acc = +0.0f
+ *     for k = 0 .. num_clients-1, in this order:
+ *         x = rows[idx[k]*row_stride + j]                 row_index NULL = identity
+ *         d = x - g;   t = coef[k] * d;   acc = acc + t
+ *     FH_NOVA_STEP:     s = tau_eff * acc;   out[j] = g + s          the whole rule, one launch
+ *     FH_NOVA_PARTIAL:  out[j] = acc          a rank's share of the sum, to all-reduce; global is
+ *                                             read, tau_eff is ignored
+ *     FH_NOVA_FINISH:   acc = rows[idx[0]*row_stride + j]   rows holds ONE row that IS the
+ *                       (all-reduced) sum, coef is not read (may be NULL), num_clients must be 1;
+ *                       s = tau_eff * acc;   out[j] = g + s
+ * Any NaN result is stored as the one quiet NaN 0x7FC00000.
+ * Aliasing: in STEP and FINISH out may be the same pointer as global; in FINISH out may also be
+ * the same pointer as rows.  Any other overlap is the caller's error.
+ * FH_E_INVALID for: mode outside 0..2; num_clients < 1; FINISH with num_clients != 1; P < 0; a
+ * non-finite tau_eff in STEP or FINISH; and, for P > 0, null rows / global / out, or a null coef
+ * outside FINISH.  P == 0 is a no-op.  No workspace.  16-byte loads and stores when row_stride % 4
+ * == 0 and rows, global and out are 16-byte aligned; a scalar path with the same bits covers
+ * everything else and the P % 4 tail.  STEP and PARTIAL read (C+1)*P floats and write P; FINISH
+ * reads 2*P and writes P. */
+#define FH_NOVA_STEP    0   /* out = g + tau_eff*acc          one launch, one rank      */
+#define FH_NOVA_PARTIAL 1   /* out = acc                      a rank's share, to all-reduce */
+#define FH_NOVA_FINISH  2   /* rows holds ONE row that IS acc: out = g + tau_eff*acc   */
+int fh_fednova_rows(const float* rows, int64_t row_stride, const int32_t* row_index,
+                    const float* coef, int32_t num_clients, int64_t P,
+                    const float* global, float tau_eff, int32_t mode,
+                    float* out, void* stream);
+
 /* ---------------- central DP-FedAvg (no reference counterpart) -------------
  * McMahan et al., "Learning Differentially Private Recurrent Language Models" (ICLR 2018): the
  * server clips every client's delta to an L2 norm C_t, averages the clipped deltas with uniform
