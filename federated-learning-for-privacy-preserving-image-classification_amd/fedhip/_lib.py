@@ -43,6 +43,9 @@ SIGNATURES = {
     "fh_secagg_sum_decode": (I32, [P, I64, P, I32, I64, P, P, I32, U64, I32, P, P, P]),
     "fh_server_opt_step": (I32, [P, I64, P, P, I32, I64, P, P, P, I32, F32, F32, F32, F32, P]),
     "fh_fednova_rows": (I32, [P, I64, P, P, I32, I64, P, F32, I32, P, P]),
+    "fh_center_iter_workspace": (SZ, [I32, I64]),
+    "fh_center_iter": (I32, [P, I64, P, P, I32, I64, P, I32, P, P, SZ, P, P]),
+    "fh_center_coef": (I32, [P, P, I32, I32, F64, P, P, P]),
     "fh_dpfa_row_sqnorm_workspace": (SZ, [I32, I64]),
     "fh_dpfa_row_sqnorm": (I32, [P, I64, P, P, I32, I64, P, SZ, P, P]),
     "fh_dpfa_clip_coef": (I32, [P, I32, I32, F64, P, P, P, P, P]),

@@ -1483,6 +1483,76 @@ def pairwise_sqdist(rows, row_index=None, P=None):
     return dist
 
 
+# ------------------------------------------------------------------ geometric median / centered clip
+CENTER_MEAN, CENTER_DELTA = 0, 1      # FH_CENTER_* of include/fedhip.h: fh_center_iter's mode
+CENTER_GEOMED, CENTER_CCLIP = 0, 1    # ... and fh_center_coef's rule
+CENTER_STATE_DOUBLES = 4
+CENTER_LIVE, CENTER_OBJECTIVE, CENTER_COEF_SUM, CENTER_PARAM = range(4)
+
+
+def _center_ws(device, C, P):
+    """The cached workspace of fh_center_iter: the size query is answered once per (C, P), the
+    buffer is the stream's grow-only scratch."""
+    key = ("fh_center_iter_workspace", C, P)
+    need = _WS_SIZE.get(key)
+    if need is None:
+        need = _WS_SIZE[key] = load().fh_center_iter_workspace(C, P)
+    return (_ws(device).get(need) if need else None), need
+
+
+def center_iter(rows, coef_f32, out, mode, center=None, row_index=None, P=None, sqdist=None):
+    """One fused launch (the arithmetic is defined in include/fedhip.h): the new centre
+      CENTER_MEAN   out = sum_k coef_k * rows[row_index[k]]
+      CENTER_DELTA  out = center + sum_k coef_k * (rows[row_index[k]] - center)
+    summed sequentially in fp32 with every coef_k == 0 skipped, AND sqdist[k] = sum_j
+    (double)fl32(rows[row_index[k], j] - out[j])^2 for every k, the rows read once.  out and
+    center are contiguous fp32 [>= P]; out may be center in DELTA.  Returns (out, sqdist),
+    sqdist a device float64 [C]."""
+    nrows, P = _dpfa_rows(rows, row_index, P, "center_iter")
+    if coef_f32 is None or out is None:
+        raise FedHipError("center_iter: coef_f32 and out are required")
+    require_device(out, "out")
+    C = coef_f32.numel()  # without a row_index: the first C rows
+    _dpfa_vec(coef_f32, torch.float32, C, "center_iter", "coef_f32")
+    if (row_index is not None and nrows != C) or nrows < C:
+        raise FedHipError(f"center_iter: {nrows} rows for {C} coefficients")
+    _dpfa_vec(out, torch.float32, P, "center_iter", "out")
+    _dpfa_vec(center, torch.float32, P, "center_iter", "center")
+    mode = int(mode)
+    if mode == CENTER_DELTA and center is None:
+        raise FedHipError("center_iter: CENTER_DELTA needs a center")
+    if sqdist is None:
+        sqdist = torch.empty(C, dtype=torch.float64, device=rows.device)
+    _dpfa_vec(sqdist, torch.float64, C, "center_iter", "sqdist")
+    ws, need = _center_ws(rows.device, C, P)
+    call("fh_center_iter", ptr(rows), rows.stride(0), ptr(row_index), ptr(coef_f32), C, P,
+         ptr(center), mode, ptr(out), ptr(ws), need, ptr(sqdist), stream_handle())
+    return out, sqdist
+
+
+def center_coef(sqdist, alpha, rule, param, coef=None, state=None):
+    """The next coefficients from the squared distances (fp64 on the device, include/fedhip.h):
+      CENTER_GEOMED  coef_k = fl32(b_k / sum b),  b_k = alpha_k / max(param, d_k)    param = nu
+      CENTER_CCLIP   coef_k = fl32(alpha_k * min(1, param / d_k))                    param = tau
+    d_k = sqrt(sqdist_k); a client with a non-finite sqdist or alpha_k <= 0 gets 0.  alpha:
+    device float64 [C].  state (float64 [CENTER_STATE_DOUBLES]): live clients, sum alpha_k * d_k,
+    sum b or sum coef, param.  Returns (coef fp32 [C], state)."""
+    require_device(sqdist, "sqdist")
+    C, dev = sqdist.numel(), sqdist.device
+    _dpfa_vec(sqdist, torch.float64, C, "center_coef", "sqdist")
+    _dpfa_vec(alpha, torch.float64, C, "center_coef", "alpha")
+    if alpha is None or alpha.numel() != C:
+        raise FedHipError(f"center_coef: alpha must hold one weight per client ({C})")
+    coef = torch.empty(C, dtype=torch.float32, device=dev) if coef is None else coef
+    state = torch.empty(CENTER_STATE_DOUBLES, dtype=torch.float64, device=dev) \
+        if state is None else state
+    _dpfa_vec(coef, torch.float32, C, "center_coef", "coef")
+    _dpfa_vec(state, torch.float64, CENTER_STATE_DOUBLES, "center_coef", "state")
+    call("fh_center_coef", ptr(sqdist), ptr(alpha), C, int(rule), float(param), ptr(coef),
+         ptr(state), stream_handle())
+    return coef, state
+
+
 def _terms(term_keys, term_signs, shape):
     """(keys ptr, signs ptr, nterms) of a term list: int64 keys (the uint64's bits) and int32
     signs, contiguous, shaped `shape` + [nterms]; None = no terms."""

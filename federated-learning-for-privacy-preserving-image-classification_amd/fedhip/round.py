@@ -18,10 +18,12 @@ all-gathers every client's row and runs the sequential FedAvg kernel over all
 clients in global client order on every rank (fedavg.py:278-285 bit for bit, at
 C x P floats of gather traffic per rank instead of one P-float all-reduce).
 
-``aggregator`` (a src.aggregation.robust rule: trimmed mean, median, Krum) replaces the FedAvg
-of the PARAMETER rows by the rule's ``aggregate_packed`` over the same rows: this rank's on one
-rank, the all-gathered rows of every client (global client order) with ``exact=True`` on
-several.  A robust rule is not a sum, so it cannot be all-reduced: several ranks without
+``aggregator`` (a src.aggregation.robust rule: trimmed mean, median, Krum, geometric median,
+centered clipping) replaces the FedAvg of the PARAMETER rows by the rule's ``aggregate_packed``
+over the same rows: this rank's on one rank, the all-gathered rows of every client (global client
+order) with ``exact=True`` on several.  A rule with ``uses_center`` (geometric median, centered
+clipping) is also handed the previous global vector as ``center=``.  A robust rule is not a sum,
+so it cannot be all-reduced: several ranks without
 ``exact`` are refused at construction.  The BN running statistics (``global_bufs``) keep the
 plain FedAvg.  With ``aggregator=None`` nothing changes.
 
@@ -362,6 +364,13 @@ class RankRound:
         return self._quant is not None and self.aggregator is None and self.central is None \
             and not self.exact and self.fednova is None
 
+    def _center_kw(self):
+        """A rule that iterates around a centre (geometric median, centered clipping) gets the
+        previous global model as that centre."""
+        if getattr(self.aggregator, "uses_center", False):
+            return {"center": self.global_flat}
+        return {}
+
     def reset_compression_state(self):
         """Forget every client's error-feedback residual (a new training run, or a new
         client-to-slot assignment, on the same RankRound)."""
@@ -429,7 +438,7 @@ class RankRound:
             else:  # the rule over every client's row, in global client order, on every rank
                 self.aggregator.aggregate_packed(self._exact_gather(tr.params, self.P),
                                                  self._x_samples, row_index=self._x_rows,
-                                                 out=agg_out)
+                                                 out=agg_out, **self._center_kw())
             if sopt is not None:
                 sopt.step_vector(self.partial, self.global_flat)
             if self.Q and not keep_bufs:
@@ -492,7 +501,8 @@ class RankRound:
                     sopt.step_vector(self.partial, self.global_flat)
         else:  # one rank (checked at construction): the rule over this rank's rows
             self.aggregator.aggregate_packed(tr.params[:, :self.P], self._agg_samples,
-                                             row_index=self._agg_rows, out=agg_out)
+                                             row_index=self._agg_rows, out=agg_out,
+                                             **self._center_kw())
             if sopt is not None:
                 sopt.step_vector(self.partial, self.global_flat)
         if self.Q and not keep_bufs:

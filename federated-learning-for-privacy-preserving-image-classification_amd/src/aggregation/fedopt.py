@@ -182,8 +182,9 @@ class ServerOptimizer:
             if self._scratch is None or self._scratch.numel() != P \
                     or self._scratch.device != packed.device:
                 self._scratch = torch.empty(P, dtype=torch.float32, device=packed.device)
+            extra = {"center": global_flat} if getattr(self.base, "uses_center", False) else {}
             self.base.aggregate_packed(packed[:, :P], num_samples, row_index=row_index,
-                                       out=self._scratch)
+                                       out=self._scratch, **extra)
             return self.step_vector(self._scratch, global_flat)
         w = self.base._calculate_sample_weights_n(list(num_samples))
         w32 = torch.tensor(w, dtype=torch.float32, device=packed.device)

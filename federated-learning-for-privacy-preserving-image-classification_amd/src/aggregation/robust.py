@@ -9,14 +9,20 @@ history and FedAvgError wrapping; only ``_weighted_average`` and ``aggregate_pac
   MedianAggregator       coordinate-wise median (Yin et al. 2018)         fh_trimmed_mean_rows
   KrumAggregator         Krum / multi-Krum (Blanchard et al. 2017)        fh_pairwise_sqdist
                                                                           + fh_fedavg_weighted_sum
+  GeometricMedianAggregator  smoothed Weiszfeld / RFA (Pillutla et al. 2022)  fh_center_iter
+  CenteredClipAggregator     centered clipping (Karimireddy et al. 2021)      + fh_center_coef
 
 The coordinate-wise rules are unweighted: a sample count is the client's own claim.  The
-counts are still recorded in the aggregation history.  Definitions: include/fedhip.h and
-DESIGN.md §5.
+counts are still recorded in the aggregation history.  The last two rules weight the clients
+(sample counts or uniform) and iterate around a centre: every iteration is one fused launch
+that reads the rows once and one small launch for the next coefficients, with no host round
+trip in between.  Definitions: include/fedhip.h and DESIGN.md §5.
 """
 from __future__ import annotations
 
+import logging
 import math
+from datetime import datetime
 from typing import List, Optional, Sequence
 
 import numpy as np
@@ -24,8 +30,11 @@ import torch
 
 from fedhip import ops
 
-from ..shared.models import ModelUpdate, ModelWeights
+from ..shared.models import GlobalModel, ModelUpdate, ModelWeights
 from .fedavg import FedAvgAggregator, FedAvgError
+
+logger = logging.getLogger(__name__)
+
 
 def trim_count(trim_ratio: float, num_clients: int) -> int:
     """Rows dropped per side: floor(trim_ratio * C)."""
@@ -165,8 +174,219 @@ class KrumAggregator(_RowRule):
         return ops.fedavg_weighted_sum(rows, w32, out, row_index=sel_idx, P=P)
 
 
+class _CenterRule(_RowRule):
+    """A rule that iterates a weighted sum of the rows around a centre: `iters` times
+    (fh_center_iter: the new centre and every client's squared distance to it, the rows read
+    once; fh_center_coef: the next coefficients), all on the device.  After the last launch
+    the small state is read back once:
+
+      last_coef       the coefficients of the last iteration (what produced the result)
+      last_rejected   the positions whose last coefficient is 0 (NaN / Inf rows, weight 0)
+      last_objective  sum_k alpha_k * ||x_k - result|| over the live clients
+      last_sqdist     device float64 [iters + 1, C]: the squared distances to the start centre
+                      and to the centre after every iteration
+    """
+    uses_center = True
+    _rule = None   # ops.CENTER_GEOMED / ops.CENTER_CCLIP
+    _mode = None   # ops.CENTER_MEAN / ops.CENTER_DELTA
+
+    def __init__(self, param: float, what: str, iters: int, weighting: str, min_clients: int,
+                 max_clients: Optional[int], validate_updates: bool,
+                 device: Optional[torch.device]):
+        if isinstance(param, bool) or not isinstance(param, (int, float)) \
+                or not math.isfinite(param) or param <= 0:
+            raise ValueError(f"{what} must be a finite positive number: {param!r}")
+        if isinstance(iters, bool) or not isinstance(iters, int) or iters < 1:
+            raise ValueError(f"iters must be an integer >= 1: {iters!r}")
+        if weighting not in ("samples", "uniform"):
+            raise ValueError(f"weighting must be 'samples' or 'uniform': {weighting!r}")
+        super().__init__(min_clients, max_clients, validate_updates, device)
+        self._param, self.iters, self.weighting = float(param), iters, weighting
+        self.last_coef: List[float] = []
+        self.last_rejected: List[int] = []
+        self.last_objective: Optional[float] = None
+        self.last_sqdist: Optional[torch.Tensor] = None
+
+    def _alpha(self, num_samples: Sequence[float]) -> List[float]:
+        """alpha_k = n_k / sum n in Python double, or 1/C."""
+        C = len(num_samples)
+        if self.weighting == "uniform":
+            return [1.0 / C] * C
+        return self._calculate_sample_weights_n(list(num_samples))
+
+    def _start(self, rows, idx, C, P, out, center):
+        """Puts the start centre where the first distance pass reads it; returns that tensor."""
+        raise NotImplementedError
+
+    def _iterate(self, rows: torch.Tensor, idx: Optional[torch.Tensor], alpha: List[float],
+                 out: torch.Tensor, center: Optional[torch.Tensor]) -> torch.Tensor:
+        C, P, n, dev = len(alpha), out.numel(), self.iters + 1, rows.device
+        if not 1 <= C <= 64:
+            raise FedAvgError(f"{type(self).__name__} takes 1..64 clients: {C}")
+        if center is not None and (center.numel() != P or center.dtype != torch.float32
+                                   or not center.is_contiguous()):
+            raise FedAvgError(f"center must be a contiguous float32 vector of {P} elements")
+        # one small buffer for everything the host reads back: n states, then n x C coefficients
+        S = ops.CENTER_STATE_DOUBLES
+        small = torch.zeros(n * S + (n * C + 1) // 2, dtype=torch.float64, device=dev)
+        state = small[:n * S].view(n, S)
+        coef = small[n * S:].view(torch.float32)[:n * C].view(n, C)
+        a64 = torch.tensor(alpha, dtype=torch.float64, device=dev)
+        sq = self.last_sqdist = torch.empty(n, C, dtype=torch.float64, device=dev)
+        v0 = self._start(rows, idx, C, P, out, center)
+        ops.dpfa_row_sqnorm(rows, v0, row_index=idx, P=P, out=sq[0])
+        ops.center_coef(sq[0], a64, self._rule, self._param, coef=coef[0], state=state[0])
+        for i in range(self.iters):
+            ops.center_iter(rows, coef[i], out, self._mode, row_index=idx, P=P, sqdist=sq[i + 1],
+                            center=out if self._mode == ops.CENTER_DELTA else None)
+            ops.center_coef(sq[i + 1], a64, self._rule, self._param, coef=coef[i + 1],
+                            state=state[i + 1])
+        host = small.cpu()  # the one read-back
+        st = host[:n * S].view(n, S)
+        self.last_coef = host[n * S:].view(torch.float32)[:n * C].view(n, C)[n - 2].tolist()
+        self.last_rejected = [k for k, c in enumerate(self.last_coef) if c == 0.0]
+        self.last_objective = float(st[n - 1, ops.CENTER_OBJECTIVE])
+        if float(st[:, ops.CENTER_LIVE].min()) == 0.0:
+            raise FedAvgError(f"{type(self).__name__}: no live client (every row is non-finite "
+                              f"or has weight 0)")
+        return out
+
+    def _reduce_rows(self, rows, idx, idx_host, C, out):
+        return self._iterate(rows, idx, self._alpha([1] * C), out, None)
+
+    def _weighted_average(self, updates: List[ModelUpdate], weights: List[float]) -> ModelWeights:
+        rows, names, offs, sizes = self._pack_updates(updates)
+        out = torch.empty(offs[-1], dtype=torch.float32, device=self.device)
+        alpha = list(weights) if self.weighting == "samples" else self._alpha(weights)
+        self._iterate(rows, None, alpha, out, None)
+        return self._unpack_row(out, updates[0].model_weights, names, offs, sizes)
+
+    def aggregate_packed(self, packed: torch.Tensor, num_samples: Sequence[int],
+                         row_index: Optional[Sequence[int]] = None,
+                         out: Optional[torch.Tensor] = None,
+                         center: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The rule over client rows already on the device ([clients, >= P] fp32), the clients
+        being `row_index` (default: every row, in order), weighted by `num_samples` (or
+        uniformly), around `center` (fp32 [P]; `out` may be `center` itself)."""
+        C = len(num_samples)
+        if C == 0:
+            raise FedAvgError("No updates to aggregate")
+        idx = None
+        if row_index is not None:
+            host = [int(i) for i in row_index]
+            if len(host) != C:
+                raise FedAvgError("row_index and num_samples differ in length")
+            idx = torch.tensor(host, dtype=torch.int32, device=packed.device)
+        elif packed.shape[0] != C:
+            raise FedAvgError(f"{packed.shape[0]} rows for {C} clients and no row_index")
+        if out is None:
+            P = center.numel() if center is not None else packed.shape[1]
+            out = torch.empty(P, dtype=torch.float32, device=packed.device)
+        return self._iterate(packed, idx, self._alpha(num_samples), out, center)
+
+    def _aggregate_around(self, updates: List[ModelUpdate], global_model: GlobalModel,
+                          weights: Optional[List[float]]) -> GlobalModel:
+        """The reference-style entry point around a global model (shaped like
+        FedNovaAggregator.aggregate_updates): the base class's filtering, truncation, weights,
+        packing and history, then the rule around `global_model`."""
+        name = type(self).__name__
+        try:
+            t0 = datetime.now()
+            self._validate_aggregation_inputs(updates, weights)
+            valid = self._filter_and_validate_updates(updates)
+            if len(valid) < self.min_clients:
+                raise FedAvgError(f"Insufficient valid updates: {len(valid)} < {self.min_clients}")
+            if self.max_clients and len(valid) > self.max_clients:
+                valid = sorted(valid, key=lambda u: u.num_samples, reverse=True)[:self.max_clients]
+            agg_w = self._calculate_sample_weights(valid) if weights is None \
+                else self._normalize_weights(weights[:len(valid)])
+            alpha = agg_w if weights is not None or self.weighting == "samples" \
+                else self._alpha(agg_w)
+            rows, names, offs, sizes = self._pack_updates(valid)
+            prev = global_model.model_weights
+            ref = valid[0].model_weights
+            for n in names:
+                if n not in prev or prev[n].shape != ref[n].shape:
+                    raise FedAvgError(f"global model has no layer {n} of shape "
+                                      f"{tuple(ref[n].shape)}")
+            g = torch.cat([prev[n].detach().to(device=self.device, dtype=torch.float32)
+                           .reshape(-1) for n in names]) if names \
+                else torch.empty(0, dtype=torch.float32, device=self.device)
+            self._iterate(rows, None, alpha, g, g)
+            total = sum(u.num_samples for u in valid)
+            avg_loss = sum(u.training_loss * w for u, w in zip(valid, agg_w))
+            gm = GlobalModel(round_number=valid[0].round_number,
+                             model_weights=self._unpack_row(g, ref, names, offs, sizes),
+                             accuracy_metrics={},
+                             participating_clients=[u.client_id for u in valid],
+                             convergence_score=0.0, created_at=datetime.now())
+            self._record_aggregation_stats(valid, agg_w, total, avg_loss,
+                                           (datetime.now() - t0).total_seconds())
+            return gm
+        except Exception as e:
+            logger.error(f"{name} aggregation failed: {e}")
+            raise FedAvgError(f"{name} aggregation failed: {e}") from e
+
+
+class GeometricMedianAggregator(_CenterRule):
+    """The geometric median argmin_v sum_k alpha_k ||x_k - v|| by `iters` smoothed Weiszfeld
+    steps ("RFA", Pillutla, Kakade, Harchaoui 2022):  v <- sum_k b_k x_k / sum_k b_k,
+    b_k = alpha_k / max(nu, ||x_k - v||).  Starts from `center` when one is given (RankRound
+    passes the previous global model), else from the coordinate-wise median.  Fewer than half
+    the total weight in arbitrary rows cannot move the result arbitrarily far; NaN / Inf rows
+    get coefficient 0."""
+    _rule, _mode = ops.CENTER_GEOMED, ops.CENTER_MEAN
+
+    def __init__(self, nu: float = 1e-6, iters: int = 3, weighting: str = "samples",
+                 min_clients: int = 2, max_clients: Optional[int] = None,
+                 validate_updates: bool = True, device: Optional[torch.device] = None):
+        super().__init__(nu, "nu", iters, weighting, min_clients, max_clients, validate_updates,
+                         device)
+        self.nu = self._param
+
+    def _start(self, rows, idx, C, P, out, center):
+        if center is not None:
+            return center
+        # no centre: the coordinate-wise median, parked in `out` (MEAN overwrites it later)
+        return ops.trimmed_mean_rows(rows, out, (C - 1) // 2, row_index=idx, P=P)
+
+
+class CenteredClipAggregator(_CenterRule):
+    """Centered clipping (Karimireddy, He, Jaggi 2021):  v <- v + sum_k alpha_k (x_k - v)
+    min(1, tau / ||x_k - v||), `iters` times, starting from the required `center` (the previous
+    global model).  No client moves the centre by more than alpha_k * tau per iteration; NaN /
+    Inf rows get coefficient 0.  The paper's client momentum is not part of this rule."""
+    _rule, _mode = ops.CENTER_CCLIP, ops.CENTER_DELTA
+
+    def __init__(self, tau: float, iters: int = 1, weighting: str = "uniform",
+                 min_clients: int = 2, max_clients: Optional[int] = None,
+                 validate_updates: bool = True, device: Optional[torch.device] = None):
+        super().__init__(tau, "tau", iters, weighting, min_clients, max_clients,
+                         validate_updates, device)
+        self.tau = self._param
+
+    def _start(self, rows, idx, C, P, out, center):
+        if center is None:
+            raise FedAvgError("CenteredClipAggregator needs a centre: pass center= (packed) or "
+                              "the global model (aggregate_updates)")
+        if out.data_ptr() != center.data_ptr():
+            out.copy_(center)  # the iterations run in place on the copy
+        return out
+
+    def aggregate_updates(self, updates: List[ModelUpdate], global_model: GlobalModel,
+                          weights: Optional[List[float]] = None) -> GlobalModel:
+        """Clips the updates around `global_model`; explicit `weights` replace the rule's
+        weighting."""
+        return self._aggregate_around(updates, global_model, weights)
+
+
 def create_robust_aggregator(kind: str, **kwargs) -> FedAvgAggregator:
-    """"trimmed_mean" | "median" | "krum" (one client kept) | "multi_krum" (n - f kept)."""
+    """"trimmed_mean" | "median" | "krum" (one client kept) | "multi_krum" (n - f kept) |
+    "geometric_median" | "centered_clip"."""
+    if kind == "geometric_median":
+        return GeometricMedianAggregator(**kwargs)
+    if kind == "centered_clip":
+        return CenteredClipAggregator(**kwargs)
     if kind == "trimmed_mean":
         return TrimmedMeanAggregator(**kwargs)
     if kind == "median":

@@ -218,6 +218,74 @@ int fh_fednova_rows(const float* rows, int64_t row_stride, const int32_t* row_in
                     const float* global, float tau_eff, int32_t mode,
                     float* out, void* stream);
 
+/* ---------------- geometric median and centered clipping (no reference counterpart) --
+ * Two robust rules that iterate a weighted sum of the client rows around a centre: the geometric
+ * median by the smoothed Weiszfeld iteration (Pillutla, Kakade, Harchaoui, "Robust Aggregation
+ * for Federated Learning", IEEE TSP 2022) and centered clipping (Karimireddy, He, Jaggi,
+ * "Learning from History for Byzantine Robust Optimization", ICML 2021).  An iteration is one
+ * fh_center_iter (the new centre AND every client's squared distance to it, the rows read once)
+ * and one fh_center_coef (the next coefficients from those distances).  DESIGN.md §5, D24.
+ *
+ * fh_center_iter.  x_kj = rows[idx[k]*row_stride + j], row_index NULL = identity; coef: device
+ * float[num_clients].  Per coordinate j; every operation is one rounded fp32 operation, never
+ * fused; denormals are kept:
+ *     acc = +0.0f
+ *     for k = 0 .. num_clients-1, in this order, SKIPPING every k whose coef[k] is +0.0f or -0.0f
+ *     (its x is not multiplied in: a NaN or Inf row with coefficient 0 cannot reach the sum):
+ *         FH_CENTER_MEAN:   t = coef[k] * x_kj;                     acc = acc + t
+ *         FH_CENTER_DELTA:  g = center[j];  d = x_kj - g;  t = coef[k] * d;  acc = acc + t
+ *     FH_CENTER_MEAN:   out[j] = acc           center is not read and may be NULL
+ *     FH_CENTER_DELTA:  out[j] = g + acc       out may be the same pointer as center
+ * Any NaN result is stored as the one quiet NaN 0x7FC00000.  In the same pass, for EVERY k
+ * (skipped ones included):
+ *     sqdist[k] = sum_j ((double)fl32(x_kj - out[j]))^2        out[j] as stored
+ * the difference fp32, squares and sums fp64 (the fh_dpfa_row_sqnorm / fh_pairwise_sqdist
+ * contract).  sqdist: device double[num_clients].  Each workgroup writes the fp64 partials of its
+ * columns to `workspace` (>= fh_center_iter_workspace(num_clients, P) bytes); a second small
+ * launch inside the call adds them (per client one wave: lane i adds workgroups i, i+64, ... in
+ * order, then a butterfly).  No atomics: the bits of sqdist are a function of num_clients, P and
+ * the alignments only, the same on every run.  No allocation, no host synchronisation.
+ * Vector loads and stores when row_stride % 4 == 0 and rows, out (and center in DELTA) are
+ * 16-byte aligned: 16 bytes per thread for num_clients <= 16, 8 bytes for 17..32 (a thread keeps
+ * every client's value of its columns and one fp64 accumulator per client in registers, which
+ * sets the width); a scalar path with the same bits of out covers odd strides, misaligned
+ * bases, the P % 4 tail and num_clients > 32.  Reads C*P floats (MEAN) or (C+1)*P (DELTA),
+ * writes P.
+ * FH_E_INVALID for: mode outside 0..1; num_clients outside 1..64; P < 0; null sqdist; and, for
+ * P > 0, null rows / coef / out, null center in DELTA, a short or null workspace.  P == 0 is a
+ * no-op on out that stores zero distances.  fh_center_iter_workspace is 0 for P <= 0 or
+ * num_clients outside 1..64. */
+#define FH_CENTER_MEAN  0   /* out = sum_k coef[k]*x_k                (geometric median)  */
+#define FH_CENTER_DELTA 1   /* out = center + sum_k coef[k]*(x_k - center)  (centered clip) */
+size_t fh_center_iter_workspace(int32_t num_clients, int64_t P);
+int fh_center_iter(const float* rows, int64_t row_stride, const int32_t* row_index,
+                   const float* coef, int32_t num_clients, int64_t P,
+                   const float* center, int32_t mode, float* out,
+                   void* workspace, size_t ws_bytes, double* sqdist, void* stream);
+
+/* fh_center_coef: one small launch, all fp64, every operation IEEE-rounded and on its own, sums
+ * left to right in k.  sqdist, alpha: device double[num_clients] (alpha: the clients' weights,
+ * e.g. n_k / sum n); coef: device float[num_clients]; state: device double[FH_CENTER_STATE_DOUBLES].
+ *     d_k    = sqrt(sqdist[k])
+ *     live_k = isfinite(sqdist[k]) && alpha[k] > 0
+ *   FH_CENTER_GEOMED, param = nu > 0 (the Weiszfeld smoothing):
+ *     b_k = live_k ? alpha[k] / max(nu, d_k) : 0;   B = ((b_0 + b_1) + ...)
+ *     coef[k] = fl32(b_k / B), all +0 if B == 0
+ *   FH_CENTER_CCLIP, param = tau > 0 (the clipping radius):
+ *     coef[k] = live_k ? fl32(alpha[k] * (d_k > tau ? tau / d_k : 1.0)) : 0
+ *   state[0] = the number of live clients
+ *   state[1] = ((o_0 + o_1) + ...), o_k = live_k ? alpha[k] * d_k : 0   (the geometric-median
+ *              objective at the centre the distances were taken to)
+ *   state[2] = B (GEOMED) or ((coef[0] + coef[1]) + ...) in fp64 (CCLIP)
+ *   state[3] = param
+ * FH_E_INVALID for: rule outside 0..1; num_clients outside 1..64; a param that is not finite and
+ * positive; null pointers. */
+#define FH_CENTER_GEOMED 0
+#define FH_CENTER_CCLIP  1
+#define FH_CENTER_STATE_DOUBLES 4
+int fh_center_coef(const double* sqdist, const double* alpha, int32_t num_clients,
+                   int32_t rule, double param, float* coef, double* state, void* stream);
+
 /* ---------------- central DP-FedAvg (no reference counterpart) -------------
  * McMahan et al., "Learning Differentially Private Recurrent Language Models" (ICLR 2018): the
  * server clips every client's delta to an L2 norm C_t, averages the clipped deltas with uniform
