@@ -1362,6 +1362,142 @@ def fednova_rows(rows, coef_f32, global_, out, tau_eff, mode, row_index=None, P=
     return out
 
 
+# ------------------------------------------------------------------ q-FedAvg
+QFA_STEP, QFA_PARTIAL, QFA_FINISH = range(3)  # FH_QFA_* of include/fedhip.h
+QFA_STATE_DOUBLES = 2
+QFA_DEN, QFA_LIVE = range(2)
+QFA_LOSS_GUARD = 1e-10  # F = loss + 1e-10, the authors' guard against a zero loss
+
+
+def qfedavg_coefficients(weights, losses, q, lipschitz, require_live=True):
+    """Host side of q-FedAvg (Li et al., ICLR 2020, Algorithm 2 with one L cancelled): from the
+    clients' weights pi_k and losses, with F_k = loss_k + 1e-10,
+        a_k = pi_k * F_k^q        b_k = pi_k * q * L * F_k^(q-1)
+    in Python double; the caller's float32 tensor rounds a to fp32, b stays fp64.  A client is
+    live when its weight is > 0 and its loss is finite and >= 0; any other client gets
+    a = b = 0 and is skipped by the kernel.  q == 0 gives a = pi, b = 0 without evaluating
+    F^(-1).  Returns (a: list[float], b: list[float]); ValueError for a non-finite or negative
+    q, a non-finite or non-positive lipschitz, mismatched lengths, a weight that is +-Inf, a
+    power that overflows a double, or no live client (unless require_live is False: a rank of
+    several may hold none)."""
+    p = [float(w) for w in weights]
+    loss = [float(x) for x in losses]
+    if len(p) != len(loss):
+        raise ValueError(f"qfedavg: {len(p)} weights for {len(loss)} losses")
+    if isinstance(q, bool) or not isinstance(q, (int, float)) or not math.isfinite(q) or q < 0:
+        raise ValueError(f"qfedavg: q must be a finite number >= 0: {q!r}")
+    if isinstance(lipschitz, bool) or not isinstance(lipschitz, (int, float)) \
+            or not math.isfinite(lipschitz) or lipschitz <= 0:
+        raise ValueError(f"qfedavg: lipschitz must be a finite number > 0: {lipschitz!r}")
+    q, L = float(q), float(lipschitz)
+    a, b, live = [], [], 0
+    for pk, lk in zip(p, loss):
+        if math.isinf(pk):
+            raise ValueError(f"qfedavg: infinite weight {pk!r}")
+        if not (pk > 0.0 and math.isfinite(lk) and lk >= 0.0):
+            a.append(0.0)
+            b.append(0.0)
+            continue
+        live += 1
+        if q == 0.0:
+            a.append(pk)
+            b.append(0.0)
+            continue
+        F = lk + QFA_LOSS_GUARD
+        try:
+            fq = F ** q
+            fq1 = F ** (q - 1.0)
+        except OverflowError as e:
+            raise ValueError(f"qfedavg: loss {lk!r} to the power q={q!r} overflows") from e
+        a.append(pk * fq)
+        b.append(((pk * q) * L) * fq1)
+    if not live and require_live:
+        raise ValueError("qfedavg: no live client (every weight is <= 0 or every loss is "
+                         "negative or not finite)")
+    return a, b
+
+
+def qfedavg_workspace(C, P):
+    """Bytes of fh_qfedavg_rows' workspace for C clients and P coordinates."""
+    key = ("fh_qfedavg_workspace", int(C), int(P))
+    need = _WS_SIZE.get(key)
+    if need is None:
+        need = _WS_SIZE[key] = load().fh_qfedavg_workspace(int(C), int(P))
+    return need
+
+
+def qfedavg_rows(rows, a_f32, b_f64, global_, out, mode, row_index=None, P=None, sqdist=None,
+                 state=None, workspace=None):
+    """One q-FedAvg call (the arithmetic is defined in include/fedhip.h), with
+    acc = sum_k a_k * (rows[row_index[k]] - global_) summed sequentially in fp32 (every a_k == 0
+    skipped), sqdist[k] = sum_j (double)fl32(rows[row_index[k], j] - global_[j])^2 for every k
+    and den = sum_k (b_k * sqdist_k + a_k) over the live k, the rows read once and den kept on
+    the device:
+      QFA_STEP     out = global_ + fl32(1/den) * acc       (out = global_ when den is not > 0)
+      QFA_PARTIAL  out = acc, state[QFA_DEN] = this call's share of den   (to all-reduce)
+      QFA_FINISH   out = global_ + fl32(1/state[QFA_DEN]) * rows[0]  (rows holds the ONE
+                   all-reduced sum, state the all-reduced den; a_f32 and b_f64 are None)
+    a_f32: device float32 [C], b_f64: device float64 [C]; global_ and out contiguous fp32
+    [>= P]; out may be global_ in STEP and FINISH.  state: device float64
+    [QFA_STATE_DOUBLES] (den, live clients).  workspace: a uint8 device tensor of at least
+    qfedavg_workspace(C, P) bytes (default: the stream's grow-only scratch).  Returns
+    (out, sqdist, state); sqdist is None in FINISH."""
+    require_device(rows, "rows")
+    for t, what in ((global_, "global_"), (out, "out"), (row_index, "row_index")):
+        if t is not None:
+            require_device(t, what)
+    if global_ is None or out is None:
+        raise FedHipError("qfedavg: global_ and out are required")
+    mode = int(mode)
+    if mode not in (QFA_STEP, QFA_PARTIAL, QFA_FINISH):
+        raise FedHipError(f"qfedavg: mode={mode} outside [0, 2]")
+    nrows, P = _dpfa_rows(rows, row_index, P, "qfedavg")
+    P = int(P)
+    _dpfa_vec(global_, torch.float32, P, "qfedavg", "global_")
+    _dpfa_vec(out, torch.float32, P, "qfedavg", "out")
+    dev = rows.device
+    if mode == QFA_FINISH:
+        if a_f32 is not None or b_f64 is not None:
+            raise FedHipError("qfedavg: FINISH takes the all-reduced sum, not coefficients")
+        if nrows != 1:
+            raise FedHipError(f"qfedavg: FINISH takes ONE row, the all-reduced sum (got {nrows})")
+        if state is None:
+            raise FedHipError("qfedavg: FINISH reads the all-reduced den from state")
+        _dpfa_vec(state, torch.float64, QFA_STATE_DOUBLES, "qfedavg", "state")
+        call("fh_qfedavg_rows", ptr(rows), rows.stride(0), ptr(row_index), None, None, 1, P,
+             ptr(global_), mode, ptr(out), None, 0, None, ptr(state), stream_handle())
+        return out, None, state
+    if a_f32 is None or b_f64 is None:
+        raise FedHipError("qfedavg: a_f32 and b_f64 are required outside FINISH")
+    C = a_f32.numel()  # without a row_index: the first C rows
+    if C < 1 or C > 64:
+        raise FedHipError(f"qfedavg: {C} clients outside [1, 64]")
+    _dpfa_vec(a_f32, torch.float32, C, "qfedavg", "a_f32")
+    _dpfa_vec(b_f64, torch.float64, C, "qfedavg", "b_f64")
+    if b_f64.numel() != C:
+        raise FedHipError(f"qfedavg: {b_f64.numel()} b for {C} a")
+    if (row_index is not None and nrows != C) or nrows < C:
+        raise FedHipError(f"qfedavg: {nrows} rows for {C} coefficients")
+    if mode == QFA_PARTIAL and P and out.data_ptr() == global_.data_ptr():
+        raise FedHipError("qfedavg: PARTIAL's out cannot be global_")
+    if sqdist is None:
+        sqdist = torch.empty(C, dtype=torch.float64, device=dev)
+    if state is None:
+        state = torch.empty(QFA_STATE_DOUBLES, dtype=torch.float64, device=dev)
+    _dpfa_vec(sqdist, torch.float64, C, "qfedavg", "sqdist")
+    _dpfa_vec(state, torch.float64, QFA_STATE_DOUBLES, "qfedavg", "state")
+    need = qfedavg_workspace(C, P)
+    if workspace is None:
+        workspace = _ws(dev).get(need) if need else None
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise FedHipError("qfedavg: workspace must be a contiguous uint8 tensor")
+    ws_bytes = 0 if workspace is None else workspace.numel()
+    call("fh_qfedavg_rows", ptr(rows), rows.stride(0), ptr(row_index), ptr(a_f32), ptr(b_f64), C,
+         P, ptr(global_), mode, ptr(out), ptr(workspace), ws_bytes, ptr(sqdist), ptr(state),
+         stream_handle())
+    return out, sqdist, state
+
+
 # ------------------------------------------------------------------ central DP-FedAvg
 # FH_DPFA_* of include/fedhip.h: the device state block, the Philox stream words, the flags
 DPFA_STATE_DOUBLES = 8

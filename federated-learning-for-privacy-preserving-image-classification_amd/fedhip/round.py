@@ -98,6 +98,30 @@ with a robust ``aggregator`` (the rule is a weighted sum, the robust rules are n
 ``central_dp`` (its sensitivity argument needs uniform weights, D19).  The BN running statistics
 keep the plain FedAvg: they are not the product of gradient steps.  With ``fednova=None`` nothing
 changes.
+
+``qfedavg`` (``True`` or a src.aggregation.qfedavg.QFedAvgConfig) replaces the FedAvg of the
+PARAMETER rows by q-FedAvg's fairness-aware step (Li et al., ICLR 2020, Algorithm 2; DESIGN.md
+D25)
+    x_new = g + (1/den) * sum_k a_k * (x_k - g),    den = sum_k (b_k * ||x_k - g||^2 + a_k),
+    a_k = pi_k * F_k^q,    b_k = pi_k * q * L * F_k^(q-1),
+with pi_k = 1/m over all clients of the round (``weights="samples"``: the FedAvg weights) and
+L = ``lipschitz``, by default 1/lr of that ``run()`` call (the paper's estimate).  F_k is the
+paper's loss of client k AT the global model it started from: ``run(..., client_losses=)`` takes
+it from the caller (a mapping client id -> loss, or a sequence indexed by global client id).  By
+default the round's own ``ClientMetrics.loss`` stands in, the mean training loss of the client's
+last local epoch, which is already on the host; it is a proxy, not the paper's quantity.  A client
+with an empty shard (loss NaN, FedAvg weight 0) or with a negative or non-finite loss is not live:
+it is skipped.  The coefficients are host bookkeeping per ``run()``; den stays on the device.  One
+rank: one STEP over this rank's rows.  Several ranks: each rank's PARTIAL sum and share of den,
+one all-reduce of the [P] sum and one of the fp64 den, then FINISH on every rank.  ``exact=True``:
+the ranks exchange their clients' losses and run one STEP over the all-gathered rows in global
+client order.  The result lands where FedAvg's would, so ``server_opt`` composes unchanged (a
+single-row step follows).  ``dp`` and ``compression`` stay allowed; the sums from the sparse and
+packed payloads are FedAvg's, so under q-FedAvg the dense rows are rebuilt.  Refused with
+``fednova`` (two different reweightings of the same deltas), with a robust ``aggregator`` (the rule
+is a weighted sum, the robust rules are not) and with ``central_dp`` (its sensitivity argument
+needs weights that do not depend on the clients' data, D19).  The BN running statistics keep the
+plain FedAvg.  With ``qfedavg=None`` nothing changes.
 """
 from __future__ import annotations
 
@@ -129,7 +153,7 @@ class RankRound:
                  epochs: int = 1, batch: int = 32, device="cuda", dp: Optional[DPConfig] = None,
                  group=None, lanes=None, compression=None, transform=None, dp_seed=None,
                  shuffle_seed=None, exact=False, aggregator=None, server_opt=None,
-                 central_dp=None, fednova=None):
+                 central_dp=None, fednova=None, qfedavg=None):
         self.device = torch.device(device)
         self._template = template_model
         self.B, self.epochs, self.dp, self.group = batch, epochs, dp, group
@@ -165,6 +189,27 @@ class RankRound:
         else:
             fednova = None
         self.fednova = fednova
+        if qfedavg is not None and qfedavg is not False:
+            if qfedavg is True:
+                from src.aggregation.qfedavg import QFedAvgConfig
+                qfedavg = QFedAvgConfig()
+            if fednova is not None:
+                raise ops.FedHipError("qfedavg and fednova both reweight the clients' deltas, by "
+                                      "the loss and by the step count: pass one")
+            if aggregator is not None:
+                raise ops.FedHipError("qfedavg is a weighted sum of the clients' deltas and a "
+                                      "robust aggregator is not a sum: they cannot be combined")
+            if central_dp is not None:
+                raise ops.FedHipError("qfedavg weighs the clients by their losses and central_dp's "
+                                      "sensitivity argument needs weights that do not depend on "
+                                      "the data (D19): they cannot be combined")
+            nmax = len(self.all_sizes) if exact and self.distributed else len(self.clients)
+            if nmax > 64:
+                raise ops.FedHipError(f"qfedavg: {nmax} clients in one call, fh_qfedavg_rows "
+                                      f"takes at most 64")
+        else:
+            qfedavg = None
+        self.qfedavg = qfedavg
         self.central = None
         if central_dp is not None:
             if dp is not None:
@@ -227,6 +272,13 @@ class RankRound:
         # id) — independent of the rank / lane / slot it lands on
         self.shuffle_seed = secrets.randbits(62) if shuffle_seed is None else int(shuffle_seed)
         self.partial = torch.zeros(self.P, device=self.device)
+        # q-FedAvg: den and the live count stay on the device; last_qfedavg keeps the host side
+        # of the last run() (losses, a, b, L of this rank's call; no device read)
+        self._qfa_state = self._qfa_sqdist = None
+        self.last_qfedavg = None
+        if qfedavg is not None:
+            self._qfa_state = torch.zeros(ops.QFA_STATE_DOUBLES, dtype=torch.float64,
+                                          device=self.device)
         # central DP-FedAvg: its own draws come from the same round key as the update-level
         # DP's, under stream words no client id can equal.  central_noise (fp32 [P]) replaces
         # the draw (exact replay)
@@ -316,6 +368,7 @@ class RankRound:
             self._x_c32 = torch.tensor([self._nova_coef[k] for k in order], dtype=torch.float32,
                                        device=self.device)
         self._x_rows = [pos[k] for k in order]
+        self._x_order = order
         self._x_samples = [self.epochs * self.all_sizes[k] for k in order]
         self._x_mine = torch.tensor([self.slot_of[k] for k in self.clients], dtype=torch.int64,
                                     device=self.device)
@@ -355,14 +408,15 @@ class RankRound:
 
     def _sparse_sum(self):
         """Whether this round's parameter aggregate is summed from the sparse payload: the plain
-        FedAvg routes.  Exact mode, a robust rule, central DP and FedNova read dense rows."""
+        FedAvg routes.  Exact mode, a robust rule, central DP, FedNova and q-FedAvg read dense
+        rows."""
         return self._sparse is not None and self.aggregator is None and self.central is None \
-            and not self.exact and self.fednova is None
+            and not self.exact and self.fednova is None and self.qfedavg is None
 
     def _quant_sum(self):
         """The same for the packed quantised payload."""
         return self._quant is not None and self.aggregator is None and self.central is None \
-            and not self.exact and self.fednova is None
+            and not self.exact and self.fednova is None and self.qfedavg is None
 
     def _center_kw(self):
         """A rule that iterates around a centre (geometric median, centered clipping) gets the
@@ -371,6 +425,44 @@ class RankRound:
             return {"center": self.global_flat}
         return {}
 
+    def _qfa_losses(self, metrics, client_losses):
+        """{client id: F_k} of this rank's clients (exact mode: of every client): the caller's
+        ``client_losses`` or, by default, the round's last-epoch training losses."""
+        if client_losses is None:
+            loss_of = {k: metrics[self.slot_of[k]].loss for k in self.clients}
+            if self.exact:  # every rank needs every client's loss: one host exchange
+                boxes = [None] * self._x_world
+                dist.all_gather_object(boxes, loss_of, group=self.group)
+                loss_of = {k: v for box in boxes for k, v in box.items()}
+            return loss_of
+        need = self._x_order if self.exact else self.clients
+        if hasattr(client_losses, "keys"):
+            missing = [k for k in need if k not in client_losses]
+            if missing:
+                raise ops.FedHipError(f"qfedavg: client_losses has no loss for clients {missing}")
+            return {k: float(client_losses[k]) for k in need}
+        if len(client_losses) != len(self.all_sizes):
+            raise ops.FedHipError(f"qfedavg: {len(client_losses)} client_losses for "
+                                  f"{len(self.all_sizes)} clients (indexed by global client id)")
+        return {k: float(client_losses[k]) for k in need}
+
+    def _qfa_coef(self, clients, loss_of, lr, require_live):
+        """(a fp32 [C], b fp64 [C]) on the device for `clients` in that order; pi_k is 1/m over
+        ALL clients of the round, or the FedAvg weight."""
+        cfg = self.qfedavg
+        m = len(self.all_sizes)
+        pi = [1.0 / m if cfg.weights == "uniform" else self.weights[k] for k in clients]
+        losses = [loss_of[k] for k in clients]
+        try:
+            L = cfg.lipschitz if cfg.lipschitz is not None else 1.0 / lr
+            a, b = ops.qfedavg_coefficients(pi, losses, cfg.q, L, require_live=require_live)
+        except (ValueError, ZeroDivisionError) as e:
+            raise ops.FedHipError(f"qfedavg: {e}") from e
+        self.last_qfedavg = {"clients": list(clients), "losses": losses, "a": a, "b": b,
+                             "lipschitz": L}
+        return (torch.tensor(a, dtype=torch.float32, device=self.device),
+                torch.tensor(b, dtype=torch.float64, device=self.device))
+
     def reset_compression_state(self):
         """Forget every client's error-feedback residual (a new training run, or a new
         client-to-slot assignment, on the same RankRound)."""
@@ -378,8 +470,12 @@ class RankRound:
             self.residual.zero_()
 
     def run(self, data, labels, slot_offsets: Sequence[int], optimizer_type="sgd", lr=0.01,
-            seed=0, generator=None, serialize_lanes=False):
-        """One round. data/labels: this rank's train shards, slot k's at slot_offsets[k]."""
+            seed=0, generator=None, serialize_lanes=False, client_losses=None):
+        """One round. data/labels: this rank's train shards, slot k's at slot_offsets[k].
+        client_losses (only with ``qfedavg``): every client's loss at the global model the round
+        starts from, a mapping client id -> loss or a sequence indexed by global client id."""
+        if client_losses is not None and self.qfedavg is None:
+            raise ops.FedHipError("client_losses is q-FedAvg's input: pass qfedavg= to RankRound")
         tr = self.trainer
         S = len(self.slots)
         _t = [time.perf_counter()] if _HOST_TIMING else None
@@ -433,6 +529,12 @@ class RankRound:
                 ops.fednova_rows(self._exact_gather(tr.params, self.P), self._x_c32,
                                  self.global_flat, agg_out, self._nova_tau, ops.NOVA_STEP,
                                  row_index=self._x_idx, P=self.P)
+            elif self.qfedavg is not None:  # one STEP over every client's row, global order
+                a32, b64 = self._qfa_coef(self._x_order, self._qfa_losses(metrics, client_losses),
+                                          lr, True)
+                ops.qfedavg_rows(self._exact_gather(tr.params, self.P), a32, b64,
+                                 self.global_flat, agg_out, ops.QFA_STEP, row_index=self._x_idx,
+                                 P=self.P, state=self._qfa_state)
             elif self.aggregator is None:
                 self._exact_fedavg(tr.params, self.P, agg_out)
             else:  # the rule over every client's row, in global client order, on every rank
@@ -475,6 +577,27 @@ class RankRound:
                 dist.all_reduce(self.partial, op=dist.ReduceOp.SUM, group=self.group)
                 ops.fednova_rows(self.partial.view(1, -1), None, self.global_flat, agg_out,
                                  self._nova_tau, ops.NOVA_FINISH, P=self.P)
+            if sopt is not None:
+                sopt.step_vector(self.partial, self.global_flat)
+        elif self.qfedavg is not None:
+            loss_of = self._qfa_losses(metrics, client_losses)
+            if not distributed:  # one call: the whole rule over this rank's rows
+                a32, b64 = self._qfa_coef(self.clients, loss_of, lr, True)
+                ops.qfedavg_rows(tr.params, a32, b64, self.global_flat, agg_out, ops.QFA_STEP,
+                                 row_index=self.rows, P=self.P, state=self._qfa_state)
+            else:  # this rank's shares of the sum and of den, two all-reduces, every rank finishes
+                if self.clients:  # a rank without a live client adds zeros to both
+                    a32, b64 = self._qfa_coef(self.clients, loss_of, lr, False)
+                    ops.qfedavg_rows(tr.params, a32, b64, self.global_flat, self.partial,
+                                     ops.QFA_PARTIAL, row_index=self.rows, P=self.P,
+                                     state=self._qfa_state)
+                else:
+                    self.partial.zero_()
+                    self._qfa_state.zero_()
+                dist.all_reduce(self.partial, op=dist.ReduceOp.SUM, group=self.group)
+                dist.all_reduce(self._qfa_state, op=dist.ReduceOp.SUM, group=self.group)
+                ops.qfedavg_rows(self.partial.view(1, -1), None, None, self.global_flat, agg_out,
+                                 ops.QFA_FINISH, P=self.P, state=self._qfa_state)
             if sopt is not None:
                 sopt.step_vector(self.partial, self.global_flat)
         elif self.aggregator is None:

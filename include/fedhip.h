@@ -286,6 +286,72 @@ int fh_center_iter(const float* rows, int64_t row_stride, const int32_t* row_ind
 int fh_center_coef(const double* sqdist, const double* alpha, int32_t num_clients,
                    int32_t rule, double param, float* coef, double* state, void* stream);
 
+/* ---------------- q-FedAvg, fairness-aware aggregation (no reference counterpart) --
+ * Li, Sanjabi, Beirami, Smith, "Fair Resource Allocation in Federated Learning" (ICLR 2020),
+ * Algorithm 2 with one L cancelled from the numerator and the denominator.  g is the global model
+ * the clients started from, x_kj = rows[idx[k]*row_stride + j] (row_index NULL = identity), pi_k
+ * the client's weight, F_k >= 0 its loss, q >= 0, L > 0.  The host passes
+ *     a[k] = fl32(pi_k * F_k^q)                  device float[num_clients]
+ *     b[k] = pi_k * q * L * F_k^(q-1)            device double[num_clients]
+ * (fedhip/ops.py qfedavg_coefficients) and the server sets
+ *     den   = sum_k ( b[k] * ||x_k - g||^2 + a[k] )
+ *     g_new = g + (1/den) * sum_k a[k] * (x_k - g).
+ * One call reads the client rows once and keeps den on the device.  DESIGN.md §5, D25.
+ *
+ * Per coordinate j; every operation is one rounded fp32 operation, never fused; denormals are
+ * kept:
+ *     g = global[j];  acc = +0.0f
+ *     for k = 0 .. num_clients-1, in this order, SKIPPING every k whose a[k] is +0.0f or -0.0f
+ *     (its x is not multiplied in: a NaN or Inf row with a[k] = 0 cannot reach the sum):
+ *         d = x_kj - g;   t = a[k] * d;   acc = acc + t
+ * In the same pass, for EVERY k (skipped ones included):
+ *     sqdist[k] = sum_j ((double)fl32(x_kj - g))^2
+ * the difference fp32, squares and sums fp64 (the fh_dpfa_row_sqnorm / fh_center_iter contract).
+ * sqdist: device double[num_clients].  Each workgroup writes the fp64 partials of its columns to
+ * `workspace`; a second small launch adds them (per client one wave: lane i adds workgroups i,
+ * i+64, ... in order, then a butterfly) and forms, all fp64, every operation on its own, left to
+ * right in k:
+ *     live_k = a[k] != 0
+ *     h_k    = live_k ? b[k] * sqdist[k] + (double)a[k] : 0
+ *     state[0] = den = ((h_0 + h_1) + ...)          state[1] = the number of live clients
+ * No atomics: the bits of sqdist and den are a function of num_clients, P and the alignments
+ * only, the same on every run.  With
+ *     inv = (isfinite(den) && den > 0) ? fl32(1.0 / den) : +0.0f           (fp64 division)
+ *   FH_QFA_STEP:     s = inv * acc;   out[j] = g + s.   When inv == 0, out[j] = g bit for bit
+ *                    (nothing is multiplied: no 0 * NaN).  acc lives in the workspace between
+ *                    the passes; out may be the same pointer as global.
+ *   FH_QFA_PARTIAL:  out[j] = acc     a rank's share of the sum, to all-reduce; state[0] is this
+ *                    call's share of den, to all-reduce in fp64.  out cannot be global.
+ *   FH_QFA_FINISH:   acc = rows[idx[0]*row_stride + j]: rows holds ONE row that IS the
+ *                    (all-reduced) sum, num_clients must be 1; state[0] is READ (the all-reduced
+ *                    den); out[j] = g + inv * acc as in STEP.  a, b, sqdist may be NULL; no
+ *                    workspace; out may be the same pointer as global or as rows.
+ * Any NaN result of an arithmetic operation is stored as the one quiet NaN 0x7FC00000.
+ * workspace: >= fh_qfedavg_workspace(num_clients, P) bytes, 8-byte aligned (P floats of acc, then
+ * the partials).  No allocation, no host synchronisation, a fixed number of launches (at most
+ * five).  Vector loads and stores when row_stride % 4 == 0 and rows, global and where acc goes
+ * (the workspace in STEP, out in PARTIAL) are 16-byte aligned: 16 bytes per thread for
+ * num_clients <= 16, 8 bytes for 17..32 (a thread keeps every client's value of its columns and
+ * one fp64 accumulator per client in registers, which sets the width); a scalar path with the
+ * same bits of out covers odd strides, misaligned bases, the P % 4 tail and num_clients > 32.
+ * The main pass reads (C+1)*P floats and writes P; STEP's second pass reads 2*P and writes P, as
+ * does FINISH.
+ * FH_E_INVALID for: mode outside 0..2; num_clients outside 1..64 (not exactly 1 in FINISH);
+ * P < 0; null state; null a / b / sqdist outside FINISH; and, for P > 0, null rows / global /
+ * out, a short, null or misaligned workspace outside FINISH, PARTIAL with out == global.
+ * P == 0 stores zero distances and den from the a[k] alone and touches no out.
+ * fh_qfedavg_workspace is 0 for P <= 0 or num_clients outside 1..64. */
+#define FH_QFA_STEP    0   /* out = g + acc/den              the whole rule, one rank     */
+#define FH_QFA_PARTIAL 1   /* out = acc, state[0] = den      a rank's shares, to all-reduce */
+#define FH_QFA_FINISH  2   /* rows holds ONE row that IS acc, state[0] IS den: out = g + acc/den */
+#define FH_QFA_STATE_DOUBLES 2   /* [0] den, [1] number of live clients */
+size_t fh_qfedavg_workspace(int32_t num_clients, int64_t P);
+int fh_qfedavg_rows(const float* rows, int64_t row_stride, const int32_t* row_index,
+                    const float* a, const double* b, int32_t num_clients, int64_t P,
+                    const float* global, int32_t mode, float* out,
+                    void* workspace, size_t ws_bytes,
+                    double* sqdist, double* state, void* stream);
+
 /* ---------------- central DP-FedAvg (no reference counterpart) -------------
  * McMahan et al., "Learning Differentially Private Recurrent Language Models" (ICLR 2018): the
  * server clips every client's delta to an L2 norm C_t, averages the clipped deltas with uniform
