@@ -48,6 +48,8 @@ SIGNATURES = {
     "fh_center_coef": (I32, [P, P, I32, I32, F64, P, P, P]),
     "fh_qfedavg_workspace": (SZ, [I32, I64]),
     "fh_qfedavg_rows": (I32, [P, I64, P, P, P, I32, I64, P, I32, P, P, SZ, P, P, P]),
+    "fh_fltrust_workspace": (SZ, [I32, I64]),
+    "fh_fltrust_rows": (I32, [P, I64, P, I32, I64, P, P, I32, P, P, SZ, P, P, P, P, P]),
     "fh_dpfa_row_sqnorm_workspace": (SZ, [I32, I64]),
     "fh_dpfa_row_sqnorm": (I32, [P, I64, P, P, I32, I64, P, SZ, P, P]),
     "fh_dpfa_clip_coef": (I32, [P, I32, I32, F64, P, P, P, P, P]),

@@ -27,6 +27,7 @@ a round.
 from __future__ import annotations
 
 import atexit
+import gc
 import math
 import os
 import secrets
@@ -504,17 +505,28 @@ class PackedTrainer:
             prog = None
             # capture on this trainer's own stream when it has one, so the split-K scratch
             # (keyed by stream) is the lane's, never shared with a concurrently running lane
-            with torch.cuda.graph(graph, pool=self._graph_pool, stream=self.stream):
-                rec = ops.Program.record_begin() if mode == "program" else None
-                try:
-                    self._gather(data, labels, views, n, sample_elems)
-                    self._step_launches(n, views["counts"], views["reset"], first=False,
-                                        adam_dev=views["adam"], fuse_update=True)
-                finally:
-                    net._src = None
-                    ops.conv_pair_reset()
-                    if rec is not None:
-                        prog = ops.Program.record_end(rec)
+            # No cyclic garbage collection while the stream is capturing: a dead reference cycle
+            # that still owns another trainer's graphs (a dropped RankRound whose on_trained hook
+            # refers back to it, say) would be destroyed in the middle of the capture, the
+            # runtime refuses that, and a refusal inside a destructor aborts the process.
+            # torch.cuda.graph does not collect before it starts either.
+            gc_was_on = gc.isenabled()
+            gc.disable()
+            try:
+                with torch.cuda.graph(graph, pool=self._graph_pool, stream=self.stream):
+                    rec = ops.Program.record_begin() if mode == "program" else None
+                    try:
+                        self._gather(data, labels, views, n, sample_elems)
+                        self._step_launches(n, views["counts"], views["reset"], first=False,
+                                            adam_dev=views["adam"], fuse_update=True)
+                    finally:
+                        net._src = None
+                        ops.conv_pair_reset()
+                        if rec is not None:
+                            prog = ops.Program.record_end(rec)
+            finally:
+                if gc_was_on:
+                    gc.enable()
             net.seed_dev = None
             if prog is not None and not prog.complete_for(graph):
                 prog.release()  # fail closed: replay the graph

@@ -1498,6 +1498,81 @@ def qfedavg_rows(rows, a_f32, b_f64, global_, out, mode, row_index=None, P=None,
     return out, sqdist, state
 
 
+# ------------------------------------------------------------------ FLTrust
+FLT_SCORE, FLT_STEP = range(2)  # FH_FLT_* of include/fedhip.h
+FLT_STATE_DOUBLES = 4
+FLT_SUM, FLT_LIVE, FLT_TRUSTED, FLT_ROOT_NORM = range(4)
+FLT_MAX_CLIENTS = 64
+
+
+def fltrust_workspace(C, P):
+    """Bytes of fh_fltrust_rows' workspace for C clients and P coordinates."""
+    key = ("fh_fltrust_workspace", int(C), int(P))
+    need = _WS_SIZE.get(key)
+    if need is None:
+        need = _WS_SIZE[key] = load().fh_fltrust_workspace(int(C), int(P))
+    return need
+
+
+def fltrust_rows(rows, root, global_, out, mode, row_index=None, P=None, coef=None, trust=None,
+                 stats=None, state=None, workspace=None):
+    """One FLTrust call (the arithmetic is defined in include/fedhip.h).  With the deltas
+    d_k = rows[row_index[k]] - global_ and d0 = root - global_ (fp32), the squared norms and
+    the dot products d_k . d0 summed in fp64, the rows read once:
+      trust[k] = min(1, max(0, cos(d_k, d0)))                       (0 for a client that is not live)
+      coef[k]  = fl32(trust[k] * (|d0| / |d_k|) / sum trust)        (all +0 when nobody is trusted
+                                                                     or d0 is zero or not finite)
+      FLT_SCORE  stops there; out is not used and may be None
+      FLT_STEP   out = global_ + sum_k coef[k] * d_k, sequentially in fp32, every coef[k] == 0
+                 skipped; out = global_ bit for bit when all are 0.  out may be global_.
+    The rule ignores sample counts.  root, global_, out: contiguous fp32 [>= P]; the root is not
+    one of the rows the index names.  coef: device float32 [C]; trust: float64 [C]; stats:
+    float64 [2*C + 1] (the squared norms, the dot products, |d0|^2); state: float64
+    [FLT_STATE_DOUBLES] (sum of the scores, live clients, clients with a score > 0, |d0|).
+    workspace: a uint8 device tensor of at least fltrust_workspace(C, P) bytes (default: the
+    stream's grow-only scratch); after FLT_STEP its first C doubles are every client's squared
+    distance to out.  Returns (out, coef, trust, stats, state)."""
+    require_device(rows, "rows")
+    for t, what in ((root, "root"), (global_, "global_"), (out, "out"), (row_index, "row_index")):
+        if t is not None:
+            require_device(t, what)
+    mode = int(mode)
+    if mode not in (FLT_SCORE, FLT_STEP):
+        raise FedHipError(f"fltrust: mode={mode} outside [0, 1]")
+    if root is None or global_ is None or (out is None and mode == FLT_STEP):
+        raise FedHipError("fltrust: root, global_ and (in FLT_STEP) out are required")
+    C, P = _dpfa_rows(rows, row_index, P, "fltrust")
+    P = int(P)
+    if C < 1 or C > FLT_MAX_CLIENTS:
+        raise FedHipError(f"fltrust: {C} clients outside [1, 64]")
+    _dpfa_vec(root, torch.float32, P, "fltrust", "root")
+    _dpfa_vec(global_, torch.float32, P, "fltrust", "global_")
+    _dpfa_vec(out, torch.float32, P, "fltrust", "out")
+    dev = rows.device
+    if coef is None:
+        coef = torch.empty(C, dtype=torch.float32, device=dev)
+    if trust is None:
+        trust = torch.empty(C, dtype=torch.float64, device=dev)
+    if stats is None:
+        stats = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
+    if state is None:
+        state = torch.empty(FLT_STATE_DOUBLES, dtype=torch.float64, device=dev)
+    _dpfa_vec(coef, torch.float32, C, "fltrust", "coef")
+    _dpfa_vec(trust, torch.float64, C, "fltrust", "trust")
+    _dpfa_vec(stats, torch.float64, 2 * C + 1, "fltrust", "stats")
+    _dpfa_vec(state, torch.float64, FLT_STATE_DOUBLES, "fltrust", "state")
+    need = fltrust_workspace(C, P)
+    if workspace is None:
+        workspace = _ws(dev).get(need) if need else None
+    elif workspace.dtype != torch.uint8 or not workspace.is_contiguous():
+        raise FedHipError("fltrust: workspace must be a contiguous uint8 tensor")
+    ws_bytes = 0 if workspace is None else workspace.numel()
+    call("fh_fltrust_rows", ptr(rows), rows.stride(0), ptr(row_index), C, P, ptr(root),
+         ptr(global_), mode, ptr(out), ptr(workspace), ws_bytes, ptr(coef), ptr(trust),
+         ptr(stats), ptr(state), stream_handle())
+    return out, coef, trust, stats, state
+
+
 # ------------------------------------------------------------------ central DP-FedAvg
 # FH_DPFA_* of include/fedhip.h: the device state block, the Philox stream words, the flags
 DPFA_STATE_DOUBLES = 8

@@ -19,13 +19,28 @@ clients in global client order on every rank (fedavg.py:278-285 bit for bit, at
 C x P floats of gather traffic per rank instead of one P-float all-reduce).
 
 ``aggregator`` (a src.aggregation.robust rule: trimmed mean, median, Krum, geometric median,
-centered clipping) replaces the FedAvg of the PARAMETER rows by the rule's ``aggregate_packed``
+centered clipping, FLTrust) replaces the FedAvg of the PARAMETER rows by the rule's ``aggregate_packed``
 over the same rows: this rank's on one rank, the all-gathered rows of every client (global client
 order) with ``exact=True`` on several.  A rule with ``uses_center`` (geometric median, centered
 clipping) is also handed the previous global vector as ``center=``.  A robust rule is not a sum,
 so it cannot be all-reduced: several ranks without
 ``exact`` are refused at construction.  The BN running statistics (``global_bufs``) keep the
 plain FedAvg.  With ``aggregator=None`` nothing changes.
+
+``aggregator=FLTrustAggregator(...)`` with ``trust_root=<global client id>`` (Cao et al., NDSS
+2021): that client's shard is the server's clean root dataset.  It trains like every
+other client (the step programs, lanes, ``dp``, ``compression`` and the BN-buffer FedAvg do not
+know about it); its trained row is the reference direction and is left out of the sum.  Every
+other client's delta is scored by its cosine with the root's delta, negative scores are clipped to
+zero, the deltas are rescaled to the root delta's norm and averaged with the scores as weights,
+in one ``fh_fltrust_rows`` call.  One rank: the rule runs over this rank's other rows, so the
+root must be this rank's client.  ``exact=True`` on several ranks: over the all-gathered rows in
+global client order, the root's row taken from the gather.  ``server_opt`` composes as with the
+other robust rules.  Refused: the rule without ``trust_root`` and ``trust_root`` without the rule, a
+root that is not a client of the round (on one rank: of this rank) or whose shard is empty, no
+other client or more than 64 of them, and what every robust rule refuses (several ranks without
+``exact``, ``fednova``, ``qfedavg``, ``central_dp``).  A round in which no client is trusted raises
+FedAvgError and leaves the global vector as it was.  With ``trust_root=None`` nothing changes.
 
 ``server_opt`` (a src.aggregation.fedopt.ServerOptimizer: FedAvgM, FedAdagrad, FedAdam, FedYogi)
 replaces the assignment of the aggregate to the global PARAMETER vector by one server-optimizer
@@ -153,7 +168,7 @@ class RankRound:
                  epochs: int = 1, batch: int = 32, device="cuda", dp: Optional[DPConfig] = None,
                  group=None, lanes=None, compression=None, transform=None, dp_seed=None,
                  shuffle_seed=None, exact=False, aggregator=None, server_opt=None,
-                 central_dp=None, fednova=None, qfedavg=None):
+                 central_dp=None, fednova=None, qfedavg=None, trust_root=None):
         self.device = torch.device(device)
         self._template = template_model
         self.B, self.epochs, self.dp, self.group = batch, epochs, dp, group
@@ -175,6 +190,32 @@ class RankRound:
                 and dist.get_world_size(group) > 1:
             raise ops.FedHipError("a robust aggregator over several ranks needs exact=True: "
                                   "the rule is not a sum and cannot be all-reduced")
+        # FLTrust: the shard of client `trust_root` is the server's root dataset.  It trains
+        # like every other client; its row is the reference direction and is left out of the sum
+        uses_root = getattr(aggregator, "uses_root", False)
+        if uses_root and trust_root is None:
+            raise ops.FedHipError(f"{type(aggregator).__name__} scores the clients against the "
+                                  f"server's root update: pass trust_root=<global client id>")
+        if trust_root is not None:
+            if not uses_root:
+                raise ops.FedHipError("trust_root names the server's root shard for a rule that "
+                                      "uses one: pass aggregator=FLTrustAggregator(...)")
+            if isinstance(trust_root, bool) or not isinstance(trust_root, int) \
+                    or not 0 <= trust_root < len(self.all_sizes):
+                raise ops.FedHipError(f"trust_root={trust_root!r} is not a client of the round "
+                                      f"(0..{len(self.all_sizes) - 1})")
+            if self.all_sizes[trust_root] <= 0:
+                raise ops.FedHipError(f"trust_root={trust_root}: the root shard is empty, the "
+                                      f"server would have no update to score against")
+            gathered = bool(exact) and self.distributed
+            if not gathered and trust_root not in self.clients:
+                raise ops.FedHipError(f"trust_root={trust_root} is not one of this rank's clients "
+                                      f"{self.clients}: on one rank the root trains here")
+            nmax = (len(self.all_sizes) if gathered else len(self.clients)) - 1
+            if not 1 <= nmax <= ops.FLT_MAX_CLIENTS:
+                raise ops.FedHipError(f"fltrust: {nmax} clients beside the root in one call, "
+                                      f"fh_fltrust_rows takes 1..64")
+        self.trust_root = trust_root
         if fednova is not None and fednova is not False:
             if fednova is True:
                 from src.aggregation.fednova import FedNovaConfig
@@ -258,8 +299,10 @@ class RankRound:
             self._nova_c32 = torch.tensor([self._nova_coef[k] for k in self.clients],
                                           dtype=torch.float32, device=self.device)
         # what a robust aggregator is handed on one rank: its clients' rows and sample counts
-        self._agg_rows = [self.slot_of[k] for k in self.clients]
-        self._agg_samples = [processed[k] for k in self.clients]
+        # (without the trust root, whose row is handed over as root_row=)
+        self._agg_rows = [self.slot_of[k] for k in self.clients if k != trust_root]
+        self._agg_samples = [processed[k] for k in self.clients if k != trust_root]
+        self._agg_root = self.slot_of.get(trust_root)
         # update-level DP noise: Philox keyed by (round key, global client id, element), so
         # no two clients — on any rank or lane — ever draw the same noise; the round key
         # comes from a secret base seed (os.urandom) unless the caller fixes one (tests /
@@ -367,9 +410,11 @@ class RankRound:
         if self._nova_coef is not None:
             self._x_c32 = torch.tensor([self._nova_coef[k] for k in order], dtype=torch.float32,
                                        device=self.device)
-        self._x_rows = [pos[k] for k in order]
+        # what a robust aggregator is handed: every client but the trust root, global order
+        self._x_rows = [pos[k] for k in order if k != self.trust_root]
         self._x_order = order
-        self._x_samples = [self.epochs * self.all_sizes[k] for k in order]
+        self._x_samples = [self.epochs * self.all_sizes[k] for k in order if k != self.trust_root]
+        self._x_root = pos.get(self.trust_root)
         self._x_mine = torch.tensor([self.slot_of[k] for k in self.clients], dtype=torch.int64,
                                     device=self.device)
         self._x_buf = {}
@@ -418,12 +463,15 @@ class RankRound:
         return self._quant is not None and self.aggregator is None and self.central is None \
             and not self.exact and self.fednova is None and self.qfedavg is None
 
-    def _center_kw(self):
-        """A rule that iterates around a centre (geometric median, centered clipping) gets the
-        previous global model as that centre."""
+    def _center_kw(self, root_row=None):
+        """A rule that iterates around a centre (geometric median, centered clipping, FLTrust)
+        gets the previous global model as that centre; FLTrust also the trust root's row."""
+        kw = {}
         if getattr(self.aggregator, "uses_center", False):
-            return {"center": self.global_flat}
-        return {}
+            kw["center"] = self.global_flat
+        if self.trust_root is not None:
+            kw["root_row"] = root_row
+        return kw
 
     def _qfa_losses(self, metrics, client_losses):
         """{client id: F_k} of this rank's clients (exact mode: of every client): the caller's
@@ -540,7 +588,7 @@ class RankRound:
             else:  # the rule over every client's row, in global client order, on every rank
                 self.aggregator.aggregate_packed(self._exact_gather(tr.params, self.P),
                                                  self._x_samples, row_index=self._x_rows,
-                                                 out=agg_out, **self._center_kw())
+                                                 out=agg_out, **self._center_kw(self._x_root))
             if sopt is not None:
                 sopt.step_vector(self.partial, self.global_flat)
             if self.Q and not keep_bufs:
@@ -625,7 +673,7 @@ class RankRound:
         else:  # one rank (checked at construction): the rule over this rank's rows
             self.aggregator.aggregate_packed(tr.params[:, :self.P], self._agg_samples,
                                              row_index=self._agg_rows, out=agg_out,
-                                             **self._center_kw())
+                                             **self._center_kw(self._agg_root))
             if sopt is not None:
                 sopt.step_vector(self.partial, self.global_flat)
         if self.Q and not keep_bufs:

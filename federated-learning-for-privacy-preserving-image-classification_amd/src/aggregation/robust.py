@@ -11,6 +11,8 @@ history and FedAvgError wrapping; only ``_weighted_average`` and ``aggregate_pac
                                                                           + fh_fedavg_weighted_sum
   GeometricMedianAggregator  smoothed Weiszfeld / RFA (Pillutla et al. 2022)  fh_center_iter
   CenteredClipAggregator     centered clipping (Karimireddy et al. 2021)      + fh_center_coef
+  FLTrustAggregator          trust scores against a server root update        fh_fltrust_rows
+                             (Cao et al. 2021); not majority-based
 
 The coordinate-wise rules are unweighted: a sample count is the client's own claim.  The
 counts are still recorded in the aggregation history.  The last two rules weight the clients
@@ -380,9 +382,193 @@ class CenteredClipAggregator(_CenterRule):
         return self._aggregate_around(updates, global_model, weights)
 
 
+class FLTrustAggregator(_RowRule):
+    """FLTrust (Cao, Fang, Liu, Gong 2021): the server trains on a small clean root shard as a
+    client does; client k's delta d_k = x_k - g is scored by ts_k = max(0, cos(d_k, d0)) against
+    the server's delta d0 = r - g, rescaled to ||d0|| and averaged with the scores as weights:
+    g_new = g + sum_k ts_k (||d0|| / ||d_k||) d_k / sum_k ts_k.  Unlike the rules above it
+    judges a row by its direction, not by its position among the other rows, so it holds with a
+    malicious majority and against a scaled model-replacement row.  It needs both the global
+    model the round started from (`center`) and the server's trained row (`root_row`), which is
+    not one of the clients.  The rule ignores sample counts (the paper's Algorithm 2):
+    `num_samples` only gives the number of clients and feeds the aggregation history.
+
+    One fh_fltrust_rows call (FLT_STEP), then one small read-back:
+
+      last_trust      the scores ts_k
+      last_coef       the fp32 coefficients that produced the result
+      last_rejected   the positions whose coefficient is 0 (negative cosine, NaN / Inf rows,
+                      a client that did not move)
+      last_root_norm  ||d0||
+      last_sqdist     device float64 [C]: every client's squared distance to the result
+    """
+    uses_center = True
+    uses_root = True
+
+    def __init__(self, min_clients: int = 1, max_clients: Optional[int] = None,
+                 validate_updates: bool = True, device: Optional[torch.device] = None):
+        super().__init__(min_clients, max_clients, validate_updates, device)
+        self.last_trust: List[float] = []
+        self.last_coef: List[float] = []
+        self.last_rejected: List[int] = []
+        self.last_root_norm: Optional[float] = None
+        self.last_sqdist: Optional[torch.Tensor] = None
+        self._ws: Optional[torch.Tensor] = None
+
+    def _step(self, rows: torch.Tensor, idx: Optional[torch.Tensor], C: int, root: torch.Tensor,
+              center: torch.Tensor, out: torch.Tensor) -> torch.Tensor:
+        P, dev = out.numel(), rows.device
+        if not 1 <= C <= ops.FLT_MAX_CLIENTS:
+            raise FedAvgError(f"FLTrustAggregator takes 1..64 clients beside the root: {C}")
+        for t, what in ((center, "center"), (root, "root_row")):
+            if t.numel() != P or t.dtype != torch.float32 or not t.is_contiguous():
+                raise FedAvgError(f"{what} must be a contiguous float32 vector of {P} elements")
+        # one small buffer for everything the host reads back: state, trust, then coefficients
+        S = ops.FLT_STATE_DOUBLES
+        small = torch.zeros(S + C + (C + 1) // 2, dtype=torch.float64, device=dev)
+        state, trust = small[:S], small[S:S + C]
+        coef = small[S + C:].view(torch.float32)[:C]
+        stats = torch.empty(2 * C + 1, dtype=torch.float64, device=dev)
+        need = ops.fltrust_workspace(C, P)
+        ws = self._ws
+        if need and (ws is None or ws.numel() < need or ws.device != dev):
+            ws = self._ws = torch.empty(need, dtype=torch.uint8, device=dev)  # grow-only
+        ops.fltrust_rows(rows, root, center, out, ops.FLT_STEP, row_index=idx, P=P, coef=coef,
+                         trust=trust, stats=stats, state=state, workspace=ws if need else None)
+        self.last_sqdist = ws[:8 * C].view(torch.float64).clone() if need else None
+        host = small.cpu()  # the one read-back
+        self.last_trust = host[S:S + C].tolist()
+        self.last_coef = host[S + C:].view(torch.float32)[:C].tolist()
+        self.last_rejected = [k for k, c in enumerate(self.last_coef) if c == 0.0]
+        n0 = self.last_root_norm = float(host[ops.FLT_ROOT_NORM])
+        if not (math.isfinite(n0) and n0 > 0.0):
+            raise FedAvgError(f"FLTrustAggregator: the root update is zero or not finite "
+                              f"(norm {n0!r}); the global model is unchanged")
+        total = float(host[ops.FLT_SUM])
+        if not (math.isfinite(total) and total > 0.0):
+            raise FedAvgError(f"FLTrustAggregator: no client is trusted (every cosine with the "
+                              f"root update is <= 0 or its row is non-finite; sum of scores "
+                              f"{total!r}); the global model is unchanged")
+        return out
+
+    def _reduce_rows(self, rows, idx, idx_host, C, out):
+        raise FedAvgError("FLTrustAggregator needs the global model and the server's root "
+                          "update: pass center= and root_row= (packed) or global_model and "
+                          "server_update (aggregate_updates)")
+
+    def _weighted_average(self, updates: List[ModelUpdate], weights: List[float]) -> ModelWeights:
+        return self._reduce_rows(None, None, None, len(updates), None)  # never a plain FedAvg
+
+    def aggregate_packed(self, packed: torch.Tensor, num_samples: Sequence[int],
+                         row_index: Optional[Sequence[int]] = None,
+                         out: Optional[torch.Tensor] = None,
+                         center: Optional[torch.Tensor] = None,
+                         root_row=None) -> torch.Tensor:
+        """FLTrust over client rows already on the device ([rows, >= P] fp32), the clients being
+        `row_index` (default: every row, in order), around `center` (fp32 [P], the global model
+        the round started from; `out` may be `center` itself).  `root_row` is the server's
+        trained row: a row number of `packed` (not one of the clients') or an fp32 [P] device
+        tensor.  `num_samples` only gives the number of clients: the rule does not weight by
+        it."""
+        C = len(num_samples)
+        if C == 0:
+            raise FedAvgError("No updates to aggregate")
+        if center is None or root_row is None:
+            missing = " and ".join(n for n, v in (("center (the global model)", center),
+                                                  ("root_row (the server's trained row)",
+                                                   root_row)) if v is None)
+            raise FedAvgError(f"FLTrustAggregator needs {missing}")
+        P = center.numel()
+        idx = host = None
+        if row_index is not None:
+            host = [int(i) for i in row_index]
+            if len(host) != C:
+                raise FedAvgError("row_index and num_samples differ in length")
+            idx = torch.tensor(host, dtype=torch.int32, device=packed.device)
+        if isinstance(root_row, torch.Tensor):
+            root = root_row
+            if root.dim() == 1 and root.numel() > P and root.is_contiguous():
+                root = root[:P]
+        else:
+            r = int(root_row)
+            if not 0 <= r < packed.shape[0]:
+                raise FedAvgError(f"root_row={r} is not a row of the {packed.shape[0]}-row matrix")
+            if r in (host if host is not None else range(C)):
+                raise FedAvgError(f"root_row={r} is one of the clients: the server's row is the "
+                                  f"reference direction and is left out of the sum")
+            root = packed[r, :P]
+        if row_index is None and packed.shape[0] != C:
+            if isinstance(root_row, torch.Tensor) or packed.shape[0] < C:
+                raise FedAvgError(f"{packed.shape[0]} rows for {C} clients and no row_index")
+            # the root is a later row of the matrix: the clients are rows 0..C-1, by name
+            idx = torch.arange(C, dtype=torch.int32, device=packed.device)
+        if out is None:
+            out = torch.empty(P, dtype=torch.float32, device=packed.device)
+        return self._step(packed, idx, C, root, center, out)
+
+    def aggregate_updates(self, updates: List[ModelUpdate], global_model: GlobalModel = None,
+                          server_update=None, weights: Optional[List[float]] = None) -> GlobalModel:
+        """The reference-style entry point: the base class's filtering, truncation, packing and
+        history, then FLTrust around `global_model` with `server_update` (a ModelUpdate, or a
+        weights mapping with the global model's layers) as the root.  The rule defines its own
+        weights: passing `weights=` raises, and sample counts only feed the history."""
+        name = type(self).__name__
+        try:
+            t0 = datetime.now()
+            if weights is not None:
+                raise FedAvgError("FLTrust defines its own weights (the trust scores): weights= "
+                                  "is not accepted")
+            if not isinstance(global_model, GlobalModel) or server_update is None:
+                missing = " and ".join(
+                    n for n, ok in (("global_model (the GlobalModel the round started from)",
+                                     isinstance(global_model, GlobalModel)),
+                                    ("server_update (the server's update on its root data)",
+                                     server_update is not None)) if not ok)
+                raise FedAvgError(f"FLTrust needs {missing}; it does not fall back to FedAvg")
+            self._validate_aggregation_inputs(updates, None)
+            valid = self._filter_and_validate_updates(updates)
+            if len(valid) < self.min_clients:
+                raise FedAvgError(f"Insufficient valid updates: {len(valid)} < {self.min_clients}")
+            if self.max_clients and len(valid) > self.max_clients:
+                valid = sorted(valid, key=lambda u: u.num_samples, reverse=True)[:self.max_clients]
+            agg_w = self._calculate_sample_weights(valid)  # the history's, not the rule's
+            rows, names, offs, sizes = self._pack_updates(valid)
+            prev = global_model.model_weights
+            root_w = server_update.model_weights if isinstance(server_update, ModelUpdate) \
+                else server_update
+            ref = valid[0].model_weights
+            for what, w in (("global model", prev), ("server update", root_w)):
+                for n in names:
+                    if n not in w or w[n].shape != ref[n].shape:
+                        raise FedAvgError(f"{what} has no layer {n} of shape "
+                                          f"{tuple(ref[n].shape)}")
+
+            def flat(w):
+                return torch.cat([w[n].detach().to(device=self.device, dtype=torch.float32)
+                                  .reshape(-1) for n in names]) if names \
+                    else torch.empty(0, dtype=torch.float32, device=self.device)
+            g, root = flat(prev), flat(root_w)
+            self._step(rows, None, len(valid), root, g, g)
+            total = sum(u.num_samples for u in valid)
+            avg_loss = sum(u.training_loss * w for u, w in zip(valid, agg_w))
+            gm = GlobalModel(round_number=valid[0].round_number,
+                             model_weights=self._unpack_row(g, ref, names, offs, sizes),
+                             accuracy_metrics={},
+                             participating_clients=[u.client_id for u in valid],
+                             convergence_score=0.0, created_at=datetime.now())
+            self._record_aggregation_stats(valid, agg_w, total, avg_loss,
+                                           (datetime.now() - t0).total_seconds())
+            return gm
+        except Exception as e:
+            logger.error(f"{name} aggregation failed: {e}")
+            raise FedAvgError(f"{name} aggregation failed: {e}") from e
+
+
 def create_robust_aggregator(kind: str, **kwargs) -> FedAvgAggregator:
     """"trimmed_mean" | "median" | "krum" (one client kept) | "multi_krum" (n - f kept) |
-    "geometric_median" | "centered_clip"."""
+    "geometric_median" | "centered_clip" | "fltrust"."""
+    if kind == "fltrust":
+        return FLTrustAggregator(**kwargs)
     if kind == "geometric_median":
         return GeometricMedianAggregator(**kwargs)
     if kind == "centered_clip":

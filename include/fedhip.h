@@ -352,6 +352,69 @@ int fh_qfedavg_rows(const float* rows, int64_t row_stride, const int32_t* row_in
                     void* workspace, size_t ws_bytes,
                     double* sqdist, double* state, void* stream);
 
+/* ---------------- FLTrust, trust-scored aggregation (no reference counterpart) --
+ * Cao, Fang, Liu, Gong, "FLTrust: Byzantine-robust Federated Learning via Trust Bootstrapping"
+ * (NDSS 2021), Algorithm 2.  The server trains on a small clean root shard exactly as a client
+ * does; a client's delta is scored by its cosine with the server's delta, negative scores are
+ * clipped to zero, every delta is rescaled to the server delta's norm and the scored, rescaled
+ * deltas are averaged.  g = global is the vector the round started from, r = root the server's
+ * trained row, x_kj = rows[idx[k]*row_stride + j] (row_index NULL = identity), k < num_clients;
+ * the root is not one of the clients.  The rule ignores sample counts.  DESIGN.md §5, D26.
+ *
+ * Every fp32 operation is one rounded operation, never fused; denormals are kept; a NaN result
+ * is stored as the one quiet NaN 0x7FC00000 (canon):
+ *     d0_j = fl32(r_j - g_j)                 d_kj = fl32(x_kj - g_j)
+ *     sq0   = sum_j (double)d0_j^2           sq_k = sum_j (double)d_kj^2
+ *     dot_k = sum_j (double)d_kj * (double)d0_j          (every product is exact in fp64)
+ * and, in fp64 from here on, every operation IEEE-rounded and on its own, left to right in k:
+ *     n0 = sqrt(sq0)      n_k = sqrt(sq_k)
+ *     live_k = isfinite(sq_k) && sq_k > 0 && isfinite(dot_k)
+ *     q_k  = dot_k / (n_k * n0)
+ *     ts_k = live_k ? min(1, max(0, q_k)) : 0            (a NaN q_k gives 0)
+ *     S    = ((ts_0 + ts_1) + ...)
+ *     c_k  = fl32((ts_k * (n0 / n_k)) / S)   for ts_k > 0;  +0 for ts_k == 0;  all c_k = +0 when
+ *            sq0 is not finite or not > 0, or S is not finite or not > 0
+ *     acc_j = ((+0 + c_0*d_0j) + c_1*d_1j) + ...   SKIPPING every k with c_k == 0, whatever its
+ *                                                  row holds (no 0 * NaN)
+ *     out_j = canon(g_j + acc_j);   when every c_k == 0, out = g bit for bit (-0 and NaN payloads
+ *                                   of g included)
+ * The last two lines are fh_center_iter's FH_CENTER_DELTA arithmetic with center = g, and that is
+ * the launch that computes them.
+ *
+ * One stats pass reads the rows, g and r once ((C+2)*P floats, nothing of size P written) with
+ * 2*C + 1 fp64 accumulators per thread; each workgroup writes its partials to the workspace and a
+ * one-workgroup launch adds them (per sum one wave: lane i adds workgroups i, i+64, ... in order,
+ * then a butterfly) and evaluates the fp64 lines.  33..64 clients take two stats launches over
+ * the halves of the index list (g and r are read twice).  No atomics: the bits of every output
+ * are a function of num_clients, P and the alignments only.  No allocation, no host
+ * synchronisation.  Vector loads when row_stride % 4 == 0 and rows, root and global are 16-byte
+ * aligned: 16 bytes per thread for num_clients <= 8, 8 bytes for 9..16; a scalar path with the
+ * same kind of sums covers odd strides, misaligned bases, the P % 4 tail and num_clients > 16.
+ *   coef:  device float[num_clients], the c_k         trust: device double[num_clients], the ts_k
+ *   stats: device double[2*num_clients + 1]: sq_k, then dot_k, then sq0
+ *   state: device double[FH_FLT_STATE_DOUBLES]: S, the number of live clients, the number of
+ *          clients with ts_k > 0, n0
+ *   FH_FLT_SCORE: the two launches above; out is not used and may be NULL.
+ *   FH_FLT_STEP:  then out = the new model, by fh_center_iter (DELTA, center = global, these
+ *                 coefficients); out may be the same pointer as global.  The first num_clients
+ *                 doubles of the workspace then hold every client's squared distance to the new
+ *                 model (fh_center_iter's sqdist).
+ * workspace: >= fh_fltrust_workspace(num_clients, P) bytes, 8-byte aligned (64 doubles, P floats
+ * that keep g for the all-zero case, then the partials of either pass).
+ * FH_E_INVALID, with nothing written, for: mode outside 0..1; num_clients outside 1..64; P < 0
+ * or row_stride < 0; null coef / trust / stats / state; and, for P > 0, null rows / root /
+ * global, null out in STEP, a short, null or misaligned workspace.  P == 0 forms the state from
+ * nothing (all sums 0, all coefficients +0) and touches no out and no workspace.
+ * fh_fltrust_workspace is 0 for P <= 0 or num_clients outside 1..64. */
+#define FH_FLT_SCORE 0   /* coef, trust, stats, state                                  */
+#define FH_FLT_STEP  1   /* ... and out = g + sum_k coef[k]*(x_k - g)                  */
+#define FH_FLT_STATE_DOUBLES 4   /* [0] S, [1] live clients, [2] clients with ts > 0, [3] n0 */
+size_t fh_fltrust_workspace(int32_t num_clients, int64_t P);
+int fh_fltrust_rows(const float* rows, int64_t row_stride, const int32_t* row_index,
+                    int32_t num_clients, int64_t P, const float* root, const float* global,
+                    int32_t mode, float* out, void* workspace, size_t ws_bytes,
+                    float* coef, double* trust, double* stats, double* state, void* stream);
+
 /* ---------------- central DP-FedAvg (no reference counterpart) -------------
  * McMahan et al., "Learning Differentially Private Recurrent Language Models" (ICLR 2018): the
  * server clips every client's delta to an L2 norm C_t, averages the clipped deltas with uniform
