@@ -9,8 +9,8 @@
 // client's squared distance to v_new, from which the next coefficients follow.  Built from the
 // existing kernels that reads the [C][P] rows twice.  fh_center_iter reads them once: what
 // ||x_k - v_new||^2 needs of coordinate j is column j and the coefficients, so a thread keeps
-// the C values of its V columns in registers (as trimmed_mean_kernel does: NP slots, a power
-// of two, every register-array index a compile-time constant), forms out[j], stores it and
+// the C values of its V columns in registers (the layout of rowslots.h: NP slots, a power of
+// two, every register-array index a compile-time constant), forms out[j], stores it and
 // adds (double)fl32(x_kj - out_j)^2 to its C fp64 accumulators.  HBM-bound: (C+1)*P floats read
 // in DELTA, C*P in MEAN, P written.  At the end of its columns a wave folds its 64 x NP
 // accumulators with a halving butterfly (NP - 1 exchanges, not 6*NP), the workgroup's four
@@ -22,58 +22,11 @@
 // fh_center_coef turns the distances into the next coefficients in fp64, one 64-thread launch.
 #include <cmath>
 
-#include "fh_common.h"
+#include "rowslots.h"
 
 namespace fh {
 
-__device__ __forceinline__ float ci_canon(float x) {  // one NaN out, as fednova.hip
-    return (x != x) ? __uint_as_float(0x7FC00000u) : x;
-}
-
-// row_index == NULL reads this instead: one code path, no branch around the index load
-__device__ const int32_t ci_identity[64] = {
-    0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21,
-    22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 43,
-    44, 45, 46, 47, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63};
-
-template <int V> struct CiVec;
-template <> struct CiVec<4> { using type = float4; };
-template <> struct CiVec<2> { using type = float2; };
-template <> struct CiVec<1> { using type = float; };
-
 constexpr int CI_MAXC = 64;
-
-// Sum a[k] over the 64 lanes for every k < NP.  Stage t pairs lane l with l ^ (32 >> t): the
-// lane with that bit clear keeps the lower half of the live slots, the other the upper half,
-// each adds what its partner held of the half it keeps.  After log2(NP) stages a lane holds one
-// slot, k = sum_t ((lane & (32 >> t)) ? NP >> (t+1) : 0), summed over 2^stages lanes; the
-// remaining lane bits are a plain butterfly.  Returns that slot's wave total (in every lane that
-// shares the lane's top log2(NP) bits); *slot is its k.  A fixed order of additions.
-template <int H, int O, int NP>  // one stage: H slots kept, partner lane ^ O (compile-time indices)
-__device__ __forceinline__ void ci_fold_stage(double (&a)[NP], int lane, int& k) {
-    if constexpr (H >= 1) {
-        const bool upper = (lane & O) != 0;
-#pragma unroll
-        for (int i = 0; i < H; ++i) {
-            const double send = upper ? a[i] : a[i + H];
-            const double keep = upper ? a[i + H] : a[i];
-            a[i] = keep + __shfl_xor(send, O, 64);
-        }
-        if (upper) k += H;
-        ci_fold_stage<H / 2, O / 2, NP>(a, lane, k);
-    }
-}
-
-template <int NP>
-__device__ __forceinline__ double ci_wave_fold(double (&a)[NP], int lane, int* slot) {
-    int k = 0;
-    ci_fold_stage<NP / 2, 32, NP>(a, lane, k);
-    double s = a[0];
-#pragma unroll
-    for (int o = 32 / NP; o >= 1; o /= 2) s += __shfl_xor(s, o, 64);
-    *slot = k;
-    return s;
-}
 
 // One thread: V consecutive columns starting at begin + (tile*256 + tid)*V, tiles blockIdx.x,
 // blockIdx.x + gridDim.x, ...  V > 1 needs 4*V-byte aligned rows / center / out (the host
@@ -86,9 +39,9 @@ center_iter_kernel(const float* __restrict__ rows, int64_t row_stride,
                    const int32_t* __restrict__ row_index, const float* __restrict__ coef, int C,
                    int64_t begin, int64_t units, const float* center, float* out,
                    double* __restrict__ part, int nparts, int part0) {
-    using vec_t = typename CiVec<V>::type;
+    using vec_t = typename SlotVec<V>::type;
     __shared__ double red[4][NP];
-    const int32_t* ip = row_index ? row_index : ci_identity;
+    const int32_t* ip = row_index ? row_index : slots_identity;
     const uint32_t lane_off = threadIdx.x * V;
     double sq[NP];
 #pragma unroll
@@ -96,14 +49,10 @@ center_iter_kernel(const float* __restrict__ rows, int64_t row_stride,
     for (int64_t blk = blockIdx.x; blk * 256 < units; blk += gridDim.x) {
         if (blk * 256 + threadIdx.x >= units) break;  // only in the last tile of columns
         const int64_t col0 = begin + blk * (256 * V);
-        // All NP loads are issued before the first use, in straight-line code.  Slots past C
-        // re-read row C-1 (a cache hit, no branch) and are never used.
         vec_t raw[NP];
 #pragma unroll
-        for (int k = 0; k < NP; ++k) {
-            const int64_t r = ip[k < C ? k : C - 1];
-            raw[k] = *reinterpret_cast<const vec_t*>(rows + r * row_stride + col0 + lane_off);
-        }
+        for (int k = 0; k < NP; ++k)
+            raw[k] = slots_load<V>(rows, row_stride, ip, C, k, col0, lane_off);
         vec_t gv;
         if (MODE == FH_CENTER_DELTA) gv = *reinterpret_cast<const vec_t*>(center + col0 + lane_off);
         float res[V];
@@ -123,7 +72,7 @@ center_iter_kernel(const float* __restrict__ rows, int64_t row_stride,
                     }
                 }
             }
-            res[v] = ci_canon(MODE == FH_CENTER_DELTA ? (g + acc) : acc);
+            res[v] = canon_nan(MODE == FH_CENTER_DELTA ? (g + acc) : acc);
         }
         *reinterpret_cast<vec_t*>(out + col0 + lane_off) = *reinterpret_cast<const vec_t*>(res);
 #pragma unroll
@@ -139,19 +88,20 @@ center_iter_kernel(const float* __restrict__ rows, int64_t row_stride,
             }
         }
     }
-    int slot;
     const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-    const double s = ci_wave_fold<NP>(sq, lane, &slot);
-    if ((lane & (63 >> (31 - __builtin_clz(NP)))) == 0) red[wid][slot] = s;
+    int slot;
+    const double s = slots_wave_fold<NP>(sq, lane, &slot);
+    if (slots_owner<NP>(lane)) red[wid][slot] = s;
     __syncthreads();
     if ((int)threadIdx.x < C) {
         const int k = threadIdx.x;
-        const double v = ((red[0][k] + red[1][k]) + red[2][k]) + red[3][k];  // wave order
-        part[(int64_t)k * nparts + part0 + blockIdx.x] = v;
+        part[(int64_t)k * nparts + part0 + blockIdx.x] = slots_block_sum(red, k);
     }
 }
 
-// One wave per client: lane i adds partials i, i + 64, ... in order, then the butterfly.
+// One wave per client, in part_sum's order (rowslots.h).  Written out: with the workgroup-uniform
+// k the helper compiles to other address arithmetic than this loop (same sums, other machine
+// code); whoever changes one order changes both.
 __global__ void __launch_bounds__(64)
 center_sqdist_finish_kernel(const double* __restrict__ part, int nparts,
                             double* __restrict__ sqdist) {
@@ -162,34 +112,15 @@ center_sqdist_finish_kernel(const double* __restrict__ part, int nparts,
     if (threadIdx.x == 0) sqdist[k] = s;
 }
 
-// Workgroups of a launch over `units` threads' worth of columns: at most `cap`, every one with
-// the same number of tiles (but the last ones).  A function of units and NP alone.
-static inline int ci_np(int C) {
-    int NP = 2;
-    while (NP < C) NP *= 2;
-    return NP;
-}
-static inline int ci_vec(int NP) { return NP <= 16 ? 4 : (NP == 32 ? 2 : 1); }
-static inline int ci_grid(int64_t units, int NP) {
-    if (units <= 0) return 0;
-    const int64_t cap = NP >= 32 ? 512 : (NP == 16 ? 1024 : 2048);
-    const int64_t tiles = ceil_div(units, 256);
-    return (int)ceil_div(tiles, ceil_div(tiles, cap));
-}
-// Partials of the vector path (P/4*4 columns, V at a time, plus the scalar tail) and of the
-// all-scalar path; the workspace holds the larger of the two, so it depends on C and P only.
-static inline int ci_parts_vec(int NP, int64_t P) {
-    const int V = ci_vec(NP);
-    if (V == 1) return ci_grid(P, NP);
-    const int64_t vecP = P / 4 * 4;
-    return ci_grid(vecP / V, NP) + ci_grid(P - vecP, NP);
-}
+// 16-B columns up to 16 slots, 8-B at 32, one column at 64: the values and the fp64 accumulators
+// stay in registers.
+static constexpr int ci_vec(int NP) { return NP <= 16 ? 4 : (NP == 32 ? 2 : 1); }
 
 template <int NP, int V>
 static int ci_launch(int mode, const float* rows, int64_t row_stride, const int32_t* row_index,
                      const float* coef, int C, int64_t begin, int64_t units, const float* center,
                      float* out, double* part, int nparts, int part0, hipStream_t st) {
-    const int grid = ci_grid(units, NP);
+    const int grid = slots_grid(units, NP);
     if (mode == FH_CENTER_MEAN) {
         FH_LAUNCH((center_iter_kernel<NP, V, FH_CENTER_MEAN>), dim3(grid), dim3(256), 0, st, rows,
                   row_stride, row_index, coef, C, begin, units, center, out, part, nparts, part0);
@@ -257,9 +188,8 @@ using namespace fh;
 
 extern "C" size_t fh_center_iter_workspace(int32_t num_clients, int64_t P) {
     if (num_clients < 1 || num_clients > CI_MAXC || P <= 0) return 0;
-    const int NP = ci_np(num_clients);
-    const int parts = std::max(ci_parts_vec(NP, P), ci_grid(P, NP));
-    return (size_t)num_clients * (size_t)parts * sizeof(double);
+    const int NP = slots_np(num_clients);
+    return (size_t)num_clients * (size_t)slots_parts_max(NP, ci_vec(NP), P) * sizeof(double);
 }
 
 extern "C" int fh_center_iter(const float* rows, int64_t row_stride, const int32_t* row_index,
@@ -282,37 +212,17 @@ extern "C" int fh_center_iter(const float* rows, int64_t row_stride, const int32
         const size_t need = fh_center_iter_workspace(C, P);
         FH_REQUIRE(workspace && ws_bytes >= need,
                    "center_iter: workspace of %zu bytes, %zu needed", ws_bytes, need);
-        const int NP = ci_np(C);
-        auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-        const bool vec_ok = (row_stride % 4 == 0) && al16(rows) && al16(out) &&
-                            (mode == FH_CENTER_MEAN || al16(center));
-        // 16-B columns up to 16 slots, 8-B at 32, one column at 64: the values and the fp64
-        // accumulators stay in registers.  The scalar instances take what the
-        // vector path cannot: odd strides, misaligned pointers, the P % 4 tail.
-        const int64_t vecP = (vec_ok && ci_vec(NP) > 1) ? P / 4 * 4 : 0;
-        nparts = vecP ? ci_parts_vec(NP, P) : ci_grid(P, NP);
-        const int vparts = vecP ? ci_grid(vecP / ci_vec(NP), NP) : 0;
-        int rc = FH_OK;
-#define FH_CI_CASE(np, v)                                                                       \
-    case np:                                                                                    \
-        if (vecP)                                                                               \
-            rc = ci_launch<np, v>(mode, rows, row_stride, row_index, coef, C, 0, vecP / v,      \
-                                  center, out, part, nparts, 0, st);                            \
-        if (rc == FH_OK && vecP < P)                                                            \
-            rc = ci_launch<np, 1>(mode, rows, row_stride, row_index, coef, C, vecP, P - vecP,   \
-                                  center, out, part, nparts, vparts, st);                       \
-        break;
-        switch (NP) {
-            FH_CI_CASE(2, 4)
-            FH_CI_CASE(4, 4)
-            FH_CI_CASE(8, 4)
-            FH_CI_CASE(16, 4)
-            FH_CI_CASE(32, 2)
-            default:
-                rc = ci_launch<64, 1>(mode, rows, row_stride, row_index, coef, C, 0, P, center,
-                                      out, part, nparts, 0, st);
-        }
-#undef FH_CI_CASE
+        const int NP = slots_np(C);
+        const bool vec_ok = (row_stride % 4 == 0) && aligned16(rows, out) &&
+                            (mode == FH_CENTER_MEAN || aligned16(center));
+        const SlotsPlan plan = slots_plan(NP, ci_vec(NP), vec_ok, P);
+        nparts = plan.nparts;
+        const int rc = slots_dispatch<CI_MAXC, ci_vec>(
+            NP, plan, P, [&](auto np, auto v, int64_t begin, int64_t units, int part0) {
+                return ci_launch<decltype(np)::value, decltype(v)::value>(
+                    mode, rows, row_stride, row_index, coef, C, begin, units, center, out, part,
+                    nparts, part0, st);
+            });
         if (rc != FH_OK) return rc;
     }
     FH_LAUNCH(center_sqdist_finish_kernel, dim3(C), dim3(64), 0, st,

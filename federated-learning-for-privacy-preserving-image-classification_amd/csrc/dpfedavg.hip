@@ -150,10 +150,6 @@ __global__ void dpfa_update_kernel(double* state, const double* bit_sum, double 
 }
 
 // ---- clipped sum + noise -------------------------------------------------------------------
-__device__ __forceinline__ float dpfa_canon(float x) {  // one NaN out: x86 and the GPU differ
-    return (x != x) ? __uint_as_float(0x7FC00000u) : x;
-}
-
 template <bool SUB>
 __device__ __forceinline__ float dpfa_term(float acc, float s, float x, float g) {
     const float d = SUB ? (x - g) : x;
@@ -172,7 +168,7 @@ __device__ __forceinline__ void dpfa_term4(float4& acc, float s, const float4& x
 
 __device__ __forceinline__ float dpfa_out(float acc, float g, float nu, bool noisy, bool add_g) {
     const float t = noisy ? (acc + nu) : acc;
-    return dpfa_canon(add_g ? (g + t) : t);
+    return canon_nan(add_g ? (g + t) : t);
 }
 
 // One coordinate, rows one after the other: the partial last vector and the scalar kernel.
@@ -299,22 +295,20 @@ dpfa_sum_scalar_kernel(const float* rows, int64_t row_stride,
     }
 }
 
-constexpr int64_t DPFA_GRID_CAP = 8192;  // as fedopt's: one pass covers 8192*256*4 coordinates
-
 template <bool SUB>
 static int dpfa_sum_launch(const float* rows, int64_t row_stride, const int32_t* row_index,
                            const float* scale, int C, int64_t P, const float* global, float* out,
                            const float* sigma, const float* noise_in, uint64_t seed,
                            uint64_t stream_hi, int add_g, bool vec_ok, hipStream_t st) {
     if (vec_ok) {
-        const int grid = (int)std::min<int64_t>(ceil_div(ceil_div(P, 4), 256), DPFA_GRID_CAP);
-        FH_LAUNCH((dpfa_sum_vec4_kernel<SUB>), dim3(grid), dim3(256), 0, st, rows, row_stride,
-                  row_index, scale, C, P, global, out, sigma, noise_in, seed, stream_hi, add_g);
+        FH_LAUNCH((dpfa_sum_vec4_kernel<SUB>), dim3(stream_grid(ceil_div(P, 4))), dim3(256), 0, st,
+                  rows, row_stride, row_index, scale, C, P, global, out, sigma, noise_in, seed,
+                  stream_hi, add_g);
         FH_LAUNCH_CHECK("dpfa_sum_vec4");
     } else {
-        const int grid = (int)std::min<int64_t>(ceil_div(P, 256), DPFA_GRID_CAP);
-        FH_LAUNCH((dpfa_sum_scalar_kernel<SUB>), dim3(grid), dim3(256), 0, st, rows, row_stride,
-                  row_index, scale, C, P, global, out, sigma, noise_in, seed, stream_hi, add_g);
+        FH_LAUNCH((dpfa_sum_scalar_kernel<SUB>), dim3(stream_grid(P)), dim3(256), 0, st, rows,
+                  row_stride, row_index, scale, C, P, global, out, sigma, noise_in, seed, stream_hi,
+                  add_g);
         FH_LAUNCH_CHECK("dpfa_sum_scalar");
     }
     return FH_OK;
@@ -409,9 +403,7 @@ extern "C" int fh_dpfa_clip_sum(const float* rows, int64_t row_stride, const int
                (unsigned)flags);
     if (P == 0) return FH_OK;
     FH_REQUIRE(rows && scale && out, "dpfa_clip_sum: null pointer");
-    auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    const bool vec_ok = (row_stride % 4 == 0) && al16(rows) && al16(global) && al16(out) &&
-                        al16(noise_in);
+    const bool vec_ok = (row_stride % 4 == 0) && aligned16(rows, global, out, noise_in);
     const int add_g = (global && !(flags & FH_DPFA_NO_GLOBAL_ADD)) ? 1 : 0;
     hipStream_t st = as_stream(stream);
     if (flags & FH_DPFA_ROWS_ARE_DELTAS)

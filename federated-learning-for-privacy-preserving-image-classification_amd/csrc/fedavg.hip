@@ -117,21 +117,18 @@ extern "C" int fh_fedavg_weighted_sum(const float* rows, int64_t row_stride,
     hipStream_t st = as_stream(stream);
     // 16-B path over the 4-aligned prefix (packed rows are padded to a multiple of 64
     // floats by the engine), scalar kernel for the < 4-element tail.
-    const bool vec_ok = (row_stride % 4 == 0) && (reinterpret_cast<uintptr_t>(rows) % 16 == 0) &&
-                        (reinterpret_cast<uintptr_t>(out) % 16 == 0);
+    const bool vec_ok = (row_stride % 4 == 0) && aligned16(rows, out);
     int64_t done = 0;
     if (vec_ok && P >= 4) {
         const int64_t P4 = P / 4;
-        const int grid = (int)std::min<int64_t>(ceil_div(P4, 256), 8192);
-        FH_LAUNCH(fedavg_vec4_kernel, dim3(grid), dim3(256), 0, st, rows, row_stride,
-                           row_index, weights, num_clients, P4, out, accumulate);
+        FH_LAUNCH(fedavg_vec4_kernel, dim3(stream_grid(P4)), dim3(256), 0, st, rows, row_stride,
+                  row_index, weights, num_clients, P4, out, accumulate);
         FH_LAUNCH_CHECK("fedavg_vec4");
         done = P4 * 4;
     }
     if (done < P) {
-        const int grid = (int)std::min<int64_t>(ceil_div(P - done, 256), 8192);
-        FH_LAUNCH(fedavg_scalar_kernel, dim3(grid), dim3(256), 0, st, rows, row_stride,
-                           row_index, weights, num_clients, done, P, out, accumulate);
+        FH_LAUNCH(fedavg_scalar_kernel, dim3(stream_grid(P - done)), dim3(256), 0, st, rows,
+                  row_stride, row_index, weights, num_clients, done, P, out, accumulate);
         FH_LAUNCH_CHECK("fedavg_scalar");
     }
     return FH_OK;

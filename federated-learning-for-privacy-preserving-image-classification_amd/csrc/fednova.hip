@@ -25,10 +25,6 @@
 
 namespace fh {
 
-__device__ __forceinline__ float nova_canon(float x) {  // one NaN out, as fedopt.hip
-    return (x != x) ? __uint_as_float(0x7FC00000u) : x;
-}
-
 // acc = acc + coef * (x - g): a rounded subtract, a rounded multiply, a rounded add.
 __device__ __forceinline__ float nova_term(float acc, float c, float x, float g) {
     const float d = x - g;
@@ -38,9 +34,9 @@ __device__ __forceinline__ float nova_term(float acc, float c, float x, float g)
 
 template <int MODE>
 __device__ __forceinline__ float nova_finish(float acc, float g, float tau) {
-    if (MODE == FH_NOVA_PARTIAL) return nova_canon(acc);
+    if (MODE == FH_NOVA_PARTIAL) return canon_nan(acc);
     const float s = tau * acc;
-    return nova_canon(g + s);
+    return canon_nan(g + s);
 }
 
 template <int MODE>
@@ -120,8 +116,6 @@ fednova_scalar_kernel(const float* rows, int64_t row_stride,
     }
 }
 
-constexpr int64_t NOVA_GRID_CAP = 8192;  // as fedavg's: one pass covers 8192*256*4 coordinates
-
 template <int MODE>
 static int nova_launch(const float* rows, int64_t row_stride, const int32_t* row_index,
                        const float* coef, int C, int64_t P, const float* global, float tau,
@@ -129,16 +123,14 @@ static int nova_launch(const float* rows, int64_t row_stride, const int32_t* row
     int64_t done = 0;
     if (vec_ok && P >= 4) {
         const int64_t P4 = P / 4;
-        const int grid = (int)std::min<int64_t>(ceil_div(P4, 256), NOVA_GRID_CAP);
-        FH_LAUNCH((fednova_vec4_kernel<MODE>), dim3(grid), dim3(256), 0, st, rows, row_stride,
-                  row_index, coef, C, P4, global, tau, out);
+        FH_LAUNCH((fednova_vec4_kernel<MODE>), dim3(stream_grid(P4)), dim3(256), 0, st, rows,
+                  row_stride, row_index, coef, C, P4, global, tau, out);
         FH_LAUNCH_CHECK("fednova_vec4");
         done = P4 * 4;
     }
     if (done < P) {
-        const int grid = (int)std::min<int64_t>(ceil_div(P - done, 256), NOVA_GRID_CAP);
-        FH_LAUNCH((fednova_scalar_kernel<MODE>), dim3(grid), dim3(256), 0, st, rows, row_stride,
-                  row_index, coef, C, done, P, global, tau, out);
+        FH_LAUNCH((fednova_scalar_kernel<MODE>), dim3(stream_grid(P - done)), dim3(256), 0, st,
+                  rows, row_stride, row_index, coef, C, done, P, global, tau, out);
         FH_LAUNCH_CHECK("fednova_scalar");
     }
     return FH_OK;
@@ -165,8 +157,7 @@ extern "C" int fh_fednova_rows(const float* rows, int64_t row_stride, const int3
     FH_REQUIRE(rows && global && out && (coef || mode == FH_NOVA_FINISH),
                "fednova: null pointer");
     hipStream_t st = as_stream(stream);
-    auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    const bool vec_ok = (row_stride % 4 == 0) && al16(rows) && al16(global) && al16(out);
+    const bool vec_ok = (row_stride % 4 == 0) && aligned16(rows, global, out);
     switch (mode) {
         case FH_NOVA_STEP:
             return nova_launch<FH_NOVA_STEP>(rows, row_stride, row_index, coef, num_clients, P,

@@ -24,10 +24,6 @@ struct SoptScalars {
     float lr, beta1, beta2, omb1, omb2, tau;
 };
 
-__device__ __forceinline__ float sopt_canon(float x) {  // one NaN out: x86 and the GPU differ
-    return (x != x) ? __uint_as_float(0x7FC00000u) : x;
-}
-
 // One coordinate: aggregate a, global g, moments m / v in, g' m' v' out (v untouched for
 // FH_SOPT_MOMENTUM).  RULE is a compile-time constant: no per-coordinate branch on it.
 template <int RULE>
@@ -38,8 +34,8 @@ __device__ __forceinline__ void sopt_coord(float a, float& g, float& m, float& v
         const float bm = s.beta1 * m;
         const float mn = bm + d;
         const float st = s.lr * mn;
-        g = sopt_canon(g + st);
-        m = sopt_canon(mn);
+        g = canon_nan(g + st);
+        m = canon_nan(mn);
         return;
     }
     const float bm = s.beta1 * m;
@@ -64,9 +60,9 @@ __device__ __forceinline__ void sopt_coord(float a, float& g, float& m, float& v
     const float dn = rt + s.tau;
     const float q = mn / dn;
     const float st = s.lr * q;
-    g = sopt_canon(g + st);
-    m = sopt_canon(mn);
-    v = sopt_canon(vn);
+    g = canon_nan(g + st);
+    m = canon_nan(mn);
+    v = canon_nan(vn);
 }
 
 // ROWS: a = (((0 + w0*x0) + w1*x1) + ...) over C rows; else a = the one row (C == 1).
@@ -157,8 +153,6 @@ server_opt_scalar_kernel(const float* __restrict__ rows, int64_t row_stride,
     }
 }
 
-constexpr int64_t SOPT_GRID_CAP = 8192;  // as fedavg's: one pass covers 8192*256*4 coordinates
-
 template <int RULE, bool ROWS>
 static int sopt_launch(const float* rows, int64_t row_stride, const int32_t* row_index,
                        const float* weights, int C, int64_t P, float* global, float* m, float* v,
@@ -166,16 +160,14 @@ static int sopt_launch(const float* rows, int64_t row_stride, const int32_t* row
     int64_t done = 0;
     if (vec_ok && P >= 4) {
         const int64_t P4 = P / 4;
-        const int grid = (int)std::min<int64_t>(ceil_div(P4, 256), SOPT_GRID_CAP);
-        FH_LAUNCH((server_opt_vec4_kernel<RULE, ROWS>), dim3(grid), dim3(256), 0, st, rows,
-                  row_stride, row_index, weights, C, P4, global, m, v, s);
+        FH_LAUNCH((server_opt_vec4_kernel<RULE, ROWS>), dim3(stream_grid(P4)), dim3(256), 0, st,
+                  rows, row_stride, row_index, weights, C, P4, global, m, v, s);
         FH_LAUNCH_CHECK("server_opt_vec4");
         done = P4 * 4;
     }
     if (done < P) {
-        const int grid = (int)std::min<int64_t>(ceil_div(P - done, 256), SOPT_GRID_CAP);
-        FH_LAUNCH((server_opt_scalar_kernel<RULE, ROWS>), dim3(grid), dim3(256), 0, st, rows,
-                  row_stride, row_index, weights, C, done, P, global, m, v, s);
+        FH_LAUNCH((server_opt_scalar_kernel<RULE, ROWS>), dim3(stream_grid(P - done)), dim3(256), 0,
+                  st, rows, row_stride, row_index, weights, C, done, P, global, m, v, s);
         FH_LAUNCH_CHECK("server_opt_scalar");
     }
     return FH_OK;
@@ -213,9 +205,8 @@ extern "C" int fh_server_opt_step(const float* rows, int64_t row_stride, const i
     s.omb1 = 1.0f - beta1;
     s.omb2 = 1.0f - beta2;
     s.tau = tau;
-    auto al16 = [](const void* p) { return reinterpret_cast<uintptr_t>(p) % 16 == 0; };
-    const bool vec_ok = (row_stride % 4 == 0) && al16(rows) && al16(global) && al16(m) &&
-                        (rule == FH_SOPT_MOMENTUM || al16(v));
+    const bool vec_ok = (row_stride % 4 == 0) && aligned16(rows, global, m) &&
+                        (rule == FH_SOPT_MOMENTUM || aligned16(v));
     const bool by_rows = weights != nullptr;
 #define FH_SOPT_CASE(r)                                                                        \
     case r:                                                                                    \

@@ -120,6 +120,28 @@ inline hipError_t launch_kernel(void (*k)(P...), dim3 grid, dim3 block, size_t s
 
 inline int64_t ceil_div(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
+// Grid of a streaming (grid-stride) launch with one 256-thread workgroup per 256 units: at
+// the cap one pass of a 4-wide kernel covers 8192*256*4 coordinates.
+constexpr int64_t STREAM_GRID_CAP = 8192;
+inline int stream_grid(int64_t units) {
+    return (int)std::min<int64_t>(ceil_div(units, 256), STREAM_GRID_CAP);
+}
+
+// Every pointer on a 16-byte boundary (NULL counts): what the 16-B load / store paths need.
+template <typename... T>
+inline bool aligned16(const T*... p) {
+    return ((reinterpret_cast<uintptr_t>(p) % 16 == 0) && ...);
+}
+
+// Bytes of P floats, padded to 16: a float vector at the front of a workspace keeps what
+// follows it aligned.
+inline size_t pad16_floats(int64_t P) { return ((size_t)P * sizeof(float) + 15) / 16 * 16; }
+
+// One NaN out, whatever payload or sign the arithmetic produced: x86 and the GPU differ there.
+__device__ __forceinline__ float canon_nan(float x) {
+    return (x != x) ? __uint_as_float(0x7FC00000u) : x;
+}
+
 // ---- fast unsigned division by a launch-constant divisor ------------------
 // Round-up magic multiplier (Granlund–Montgomery); exact for n < 2^31.
 struct FastDiv {

@@ -16,7 +16,7 @@
 // lanes reading the same row broadcast), thread p owns pairs p, p+256, ... and walks the
 // columns; the rows are read from HBM once, not once per pair.  Partials go to the workspace
 // and a second small launch adds them in chunk order: no atomics, same bits on every run.
-#include "fh_common.h"
+#include "rowslots.h"
 
 namespace fh {
 
@@ -33,17 +33,6 @@ __device__ __forceinline__ uint32_t tm_key(float x) {
 __device__ __forceinline__ float tm_val(uint32_t k) {
     return __uint_as_float((k >> 31) ? (k ^ 0x80000000u) : ~k);
 }
-
-// row_index == NULL reads this instead: one code path, no branch around the index load
-__device__ const int32_t tm_identity[64] = {
-    0,  1,  2,  3,  4,  5,  6,  7,  8,  9,  10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20, 21,
-    22, 23, 24, 25, 26, 27, 28, 29, 30, 31, 32, 33, 34, 35, 36, 37, 38, 39, 40, 41, 42, 43,
-    44, 45, 46, 47, 48, 49, 50, 51, 52, 53, 54, 55, 56, 57, 58, 59, 60, 61, 62, 63};
-
-template <int V> struct TmVec;
-template <> struct TmVec<4> { using type = float4; };
-template <> struct TmVec<2> { using type = float2; };
-template <> struct TmVec<1> { using type = float; };
 
 // Batcher's odd-even merge sort of NP keys (NP a power of two), ascending.  All four loops
 // have compile-time bounds once the outer ones are unrolled.
@@ -75,25 +64,21 @@ __global__ void __launch_bounds__(256)
 trimmed_mean_kernel(const float* __restrict__ rows, int64_t row_stride,
                     const int32_t* __restrict__ row_index, int C, int trim, int64_t begin,
                     int64_t units, float* __restrict__ out) {
-    using vec_t = typename TmVec<V>::type;
+    using vec_t = typename SlotVec<V>::type;
     const int hi = C - 1 - trim;
     const float denom = (float)(C - 2 * trim);
-    const int32_t* ip = row_index ? row_index : tm_identity;
-    // A workgroup walks blocks of 256*V columns.  The row pointers are wave-uniform (SGPR
-    // base) and the lane adds one 32-bit offset, so the NP addresses cost no VGPRs.
+    const int32_t* ip = row_index ? row_index : slots_identity;
     const uint32_t lane_off = threadIdx.x * V;
     for (int64_t blk = blockIdx.x; blk * 256 < units; blk += gridDim.x) {
         if (blk * 256 + threadIdx.x >= units) break;  // only in the last block of columns
         const int64_t col0 = begin + blk * (256 * V);
-        // All NP loads are issued before the first key is formed, in straight-line code, so
-        // every row is in flight at once.  Slots past C re-read row C-1 (a cache hit, no
-        // branch) and are overwritten with the pad key below.
+        // slots_load, written out: the compiler shares this C - 1 with hi's, and through the
+        // helper it would form hi another way.  Slots past C get the pad key below.
         vec_t raw[NP];
 #pragma unroll
         for (int k = 0; k < NP; ++k) {
             const int64_t r = ip[k < C ? k : C - 1];
-            const float* rp = rows + r * row_stride + col0;
-            raw[k] = *reinterpret_cast<const vec_t*>(rp + lane_off);
+            raw[k] = *reinterpret_cast<const vec_t*>(rows + r * row_stride + col0 + lane_off);
         }
         float res[V];
 #pragma unroll
@@ -111,18 +96,21 @@ trimmed_mean_kernel(const float* __restrict__ rows, int64_t row_stride,
                 else if (k > trim && k <= hi) acc = acc + x;
             }
             acc = acc / denom;
-            res[v] = (acc != acc) ? __uint_as_float(0x7FC00000u) : acc;  // one NaN out, too
+            res[v] = canon_nan(acc);
         }
         *reinterpret_cast<vec_t*>(out + col0 + lane_off) = *reinterpret_cast<const vec_t*>(res);
     }
 }
 
+// 16-B columns up to 16 slots, 8-B at 32, one column at 64: the keys stay in registers at >= 2
+// waves per SIMD.
+static constexpr int tm_vec(int NP) { return NP <= 16 ? 4 : (NP == 32 ? 2 : 1); }
+
 template <int NP, int V>
 static int tm_launch(const float* rows, int64_t row_stride, const int32_t* row_index, int C,
                      int trim, int64_t begin, int64_t units, float* out, hipStream_t st) {
-    const int grid = (int)std::min<int64_t>(ceil_div(units, 256), 8192);
-    FH_LAUNCH((trimmed_mean_kernel<NP, V>), dim3(grid), dim3(256), 0, st, rows, row_stride,
-              row_index, C, trim, begin, units, out);
+    FH_LAUNCH((trimmed_mean_kernel<NP, V>), dim3(stream_grid(units)), dim3(256), 0, st, rows,
+              row_stride, row_index, C, trim, begin, units, out);
     FH_LAUNCH_CHECK("trimmed_mean");
     return FH_OK;
 }
@@ -231,33 +219,15 @@ extern "C" int fh_trimmed_mean_rows(const float* rows, int64_t row_stride,
     if (P == 0) return FH_OK;
     FH_REQUIRE(rows && out, "trimmed_mean: null pointer");
     hipStream_t st = as_stream(stream);
-    int NP = 2;
-    while (NP < C) NP *= 2;
-    const bool vec_ok = (row_stride % 4 == 0) && (reinterpret_cast<uintptr_t>(rows) % 16 == 0) &&
-                        (reinterpret_cast<uintptr_t>(out) % 16 == 0);
-    // 16-B columns up to 16 slots, 8-B at 32, one column at 64: the keys stay in registers
-    // at >= 2 waves per SIMD.  The scalar instances take what the vector
-    // path cannot: odd strides, misaligned pointers, the P % 4 tail.
-    const int64_t vecP = (vec_ok && NP < 64) ? (P / 4) * 4 : 0;
-    int rc = FH_OK;
-#define FH_TM_CASE(np, v)                                                                     \
-    case np:                                                                                  \
-        if (vecP) rc = tm_launch<np, v>(rows, row_stride, row_index, C, trim, 0, vecP / v, out, \
-                                        st);                                                  \
-        if (rc == FH_OK && vecP < P)                                                          \
-            rc = tm_launch<np, 1>(rows, row_stride, row_index, C, trim, vecP, P - vecP, out, st); \
-        break;
-    switch (NP) {
-        FH_TM_CASE(2, 4)
-        FH_TM_CASE(4, 4)
-        FH_TM_CASE(8, 4)
-        FH_TM_CASE(16, 4)
-        FH_TM_CASE(32, 2)
-        default:
-            rc = tm_launch<64, 1>(rows, row_stride, row_index, C, trim, 0, P, out, st);
-    }
-#undef FH_TM_CASE
-    return rc;
+    const int NP = slots_np(C);
+    const bool vec_ok = (row_stride % 4 == 0) && aligned16(rows, out);
+    // no reduction over columns here: the plan's partial counts go unused
+    return slots_dispatch<64, tm_vec>(
+        NP, slots_plan(NP, tm_vec(NP), vec_ok, P), P,
+        [&](auto np, auto v, int64_t begin, int64_t units, int) {
+            return tm_launch<decltype(np)::value, decltype(v)::value>(
+                rows, row_stride, row_index, C, trim, begin, units, out, st);
+        });
 }
 
 extern "C" size_t fh_pairwise_sqdist_workspace(int32_t num_clients, int64_t P) {

@@ -116,16 +116,22 @@ def _sq_ok(got, want, P, exact):
     return bool(np.all(np.abs(got[fin] - want[fin]) <= P * 2.0 ** -53 * want[fin]))
 
 
+# The smallest shape with two tiles per workgroup: the 64-slot scalar instance (at most 512
+# workgroups, one column per thread) over 512 * 256 + 257 columns is 514 tiles on 257 workgroups,
+# the last tile partial.
+P_TWO_TILES = 512 * 256 + 257
+
+
 @pytest.mark.parametrize("C", CS)
 def test_center_iter_bits(C):
     for ki, kind in enumerate(("normal", "smallint", "special")):
-        for P in PS:
+        for P in PS + [P_TWO_TILES] * (C == 64 and kind == "normal"):
             rows, coef, center, poisoned = _case(kind, C, P, 1000 * C + 10 * ki + P)
             vec = _place(rows, (P + 3) // 4 * 4 + 4, 0)   # 16-B columns + scalar tail
             sca = _place(rows, P | 1, 0)                  # odd stride: scalar path
             for mode in MODES:
                 want, want_sq = cr.center_iter(mode, rows, coef, center=center)
-                for view in (vec, sca):
+                for view in (vec, sca)[P == P_TWO_TILES:]:
                     got, sq = _iter(view, coef, mode, center=center)
                     tag = (kind, P, mode, view.stride(0))
                     assert cr.same_bits(got, want), tag

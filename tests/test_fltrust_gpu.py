@@ -178,10 +178,14 @@ def test_fltrust_bits(C):
 
 def test_a_workgroup_walks_two_tiles_and_two_launches():
     """33 clients (two 32-slot launches) over more columns than 512 workgroups hold in one
-    tile of 256: the grid-stride loop and the last, partial tile."""
+    tile of 256: the grid-stride loop and the last, partial tile.  512 * 256 + 257 columns on
+    an odd stride is the smallest such shape: 514 tiles on 257 workgroups."""
     C, P = 33, 512 * 256 + 300
     rows, root, g = _data(C, P, 7)
     _check(rows, root, g, _place(rows, P + 4, 0), (C, P))
+    P = 512 * 256 + 257
+    rows, root, g = _data(C, P, 8)
+    _check(rows, root, g, _place(rows, (P + 2) | 1, 0), (C, P))
 
 
 @pytest.mark.parametrize("C", [1, 2, 5, 33])

@@ -142,6 +142,13 @@ def test_qfedavg_bits(C):
         sca = _place(rows, (P + 2) | 1, 0)             # odd stride > P: scalar path
         outs = [_check(rows, a, b, g, v, (C, P, v.stride(0))) for v in (vec, sca)]
         assert qr.same_bits(outs[0], outs[1]), (C, P)  # vector and scalar paths: the same bits
+    if C == 64:
+        # The smallest shape with two tiles per workgroup: the 64-slot scalar instance (at most
+        # 512 workgroups, one column per thread) over 512 * 256 + 257 columns is 514 tiles on 257
+        # workgroups, the last tile partial.
+        P = 512 * 256 + 257
+        rows, a, b, g = _data(C, P, 1000 * C + P)
+        _check(rows, a, b, g, _place(rows, (P + 2) | 1, 0), (C, P, "two tiles"))
 
 
 @pytest.mark.parametrize("C", [1, 2, 5, 33])
