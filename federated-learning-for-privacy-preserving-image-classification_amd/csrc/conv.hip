@@ -908,7 +908,7 @@ conv_c1_pool_fwd_kernel(const float* __restrict__ x, int64_t x_cs, const float* 
     }
 }
 
-// part[z][chunk][co*9 + k], bpart[z][chunk][co]  (dwgrad_ws_bytes layout, splits = chunks).
+// part[z][chunk][co*9 + k], bpart[z][chunk][co]  (the WSlab layout, splits = chunks).
 // POOLED: dy is not materialised — the gradient of pixel (r, c) is the pooled gradient
 // gp[r/2][c/2] (planes gh x gw) if (r, c) is its window's argmax and the pooled ReLU output
 // yp there is > 0, else 0: maxpool2_bwd_kernel's routing and ReLU mask (xin at the argmax is
@@ -1420,13 +1420,6 @@ static size_t mn_ws_bytes(const Plan& p, int nclients) {
     return p.splits > 1 ? (size_t)nclients * p.splits * p.M * p.N * sizeof(float) : 0;
 }
 
-static size_t wgrad_ws_bytes(const Plan& p, int nclients) {
-    if (p.splits == 1) return 0;  // written in place
-    const size_t w = (size_t)nclients * p.splits * p.M * p.N * sizeof(float);
-    const size_t b = (size_t)nclients * p.splits * p.M * sizeof(float);
-    return ((w + 255) / 256) * 256 + b;
-}
-
 static int conv_common_check(int nclients, int batch, int cin, int h, int w, int cout, int kh,
                              int kw, int stride, int pad, int& oh, int& ow) {
     FH_REQUIRE(nclients >= 0 && batch > 0 && cin > 0 && h > 0 && w > 0 && cout > 0,
@@ -1771,6 +1764,21 @@ static int pdy_materialize(float* dy, int64_t dy_cs, const int32_t* counts, int 
                                  st);
 }
 
+// the quadrant-wave WGRAD launch for map width w (32 / 16 / 8): 64-pixel double-buffered stages
+// (spx64) or one 128-pixel stage buffer
+static int launch_dwq(int w, bool spx64, const DWArgs& d, dim3 grid, hipStream_t st) {
+    if (!spx64) {
+        if (w == 32) FH_LAUNCH((dwgrad_q_kernel<32, 128, false>), grid, dim3(256), 0, st, d);
+        else if (w == 16) FH_LAUNCH((dwgrad_q_kernel<16, 128, false>), grid, dim3(256), 0, st, d);
+        else FH_LAUNCH((dwgrad_q_kernel<8, 128, false>), grid, dim3(256), 0, st, d);
+    } else {
+        if (w == 32) FH_LAUNCH((dwgrad_q_kernel<32, 64, true>), grid, dim3(256), 0, st, d);
+        else if (w == 16) FH_LAUNCH((dwgrad_q_kernel<16, 64, true>), grid, dim3(256), 0, st, d);
+        else FH_LAUNCH((dwgrad_q_kernel<8, 64, true>), grid, dim3(256), 0, st, d);
+    }
+    return FH_OK;
+}
+
 static int flush_pending_wgrad() {
     if (!g_pend.on) return FH_OK;
     if (g_pend.pdy) {  // issued on its own: its dY must exist first
@@ -1781,10 +1789,7 @@ static int flush_pending_wgrad() {
         if (rc) return rc;
     }
     g_pend.on = false;
-    const PendingWgrad& q = g_pend;
-    if (q.w == 32) FH_LAUNCH((dwgrad_q_kernel<32, 128, false>), q.grid, dim3(256), 0, q.st, q.d);
-    else if (q.w == 16) FH_LAUNCH((dwgrad_q_kernel<16, 128, false>), q.grid, dim3(256), 0, q.st, q.d);
-    else FH_LAUNCH((dwgrad_q_kernel<8, 128, false>), q.grid, dim3(256), 0, q.st, q.d);
+    if (const int rc = launch_dwq(g_pend.w, false, g_pend.d, g_pend.grid, g_pend.st)) return rc;
     FH_LAUNCH_CHECK("conv2d_wgrad direct (held)");
     return FH_OK;
 }
@@ -2129,15 +2134,90 @@ static DWPlan plan_c1_mfma(int batch, int h, int nclients) {
     return p;
 }
 
-// byte offset of the bias partials behind the weight partials [client][split][MN] of a
-// WGRAD slab (every WGRAD path lays its workspace out this way)
+static DWPlan plan_c1(int batch, int h, int w) {  // conv_c1_wgrad_kernel: one split per chunk
+    return DWPlan{1, 1, 1, 1, conv_c1_chunks(batch, h, w), 1};
+}
+
+// ---- the WGRAD slab ---------------------------------------------------------
+// Every WGRAD path lays its workspace out the same way: the weight partials
+// [client][split][MN], then, at the next 256-byte boundary, the bias partials
+// [client][split][M].  This is the one place that says so.
 static int64_t wslab_bias_off(int nclients, int splits, int64_t MN) {
     return (int64_t)(((size_t)nclients * splits * MN * sizeof(float) + 255) / 256 * 256);
 }
 
-static size_t dwgrad_ws_bytes(const DWPlan& p, int nclients, int M, int N) {
-    const size_t wb = (size_t)nclients * p.splits * M * N * sizeof(float);
-    return ((wb + 255) / 256) * 256 + (size_t)nclients * p.splits * M * sizeof(float);
+struct WSlab {
+    int nclients, splits, MN, M;
+    float* part;       // null: a size query
+    float* bias_part;  // null unless want_bias (the caller has a db)
+    int64_t bias_off;
+    size_t bytes;  // bias partials included: a size query does not know whether db is wanted
+    WSlab(int nclients_, int splits_, int MN_, int M_, void* ws = nullptr, bool want_bias = false)
+        : nclients(nclients_), splits(splits_), MN(MN_), M(M_), part((float*)ws),
+          bias_off(wslab_bias_off(nclients_, splits_, MN_)) {
+        bias_part = ws && want_bias ? (float*)((char*)ws + bias_off) : nullptr;
+        bytes = (size_t)bias_off + (size_t)nclients * splits * M * sizeof(float);
+    }
+};
+
+static size_t wgrad_ws_bytes(const Plan& p, int nclients) {
+    if (p.splits == 1) return 0;  // the implicit GEMM writes dW / db in place
+    return WSlab(nclients, p.splits, p.M * p.N, p.M).bytes;
+}
+
+// The tail of every WGRAD arm whose kernel wrote `s`.  Deferred (fh_*_wgrad_deferred): report
+// the partials left for the optimizer step to sum — splits >= 1, also for a one-split slab
+// (r06: a reported 1 once read as "written directly" and the layer's gradient was dropped;
+// "directly" is the 0 the entry points start from, kept by the arms that bypass the slab).
+// Otherwise the reduction launch, checked under the caller's label.
+static int wgrad_finish(const WSlab& s, float* dw, int64_t dw_cs, float* db, int64_t db_cs,
+                        hipStream_t st, int32_t* defer_splits, int64_t* defer_boff,
+                        const char* name) {
+    if (defer_splits) {
+        *defer_splits = s.splits;
+        *defer_boff = s.bias_off;
+        return FH_OK;
+    }
+    if (const int rc = splitk_sum(s.part, dw, dw_cs, s.splits, s.MN, s.bias_part, db, db_cs, s.M,
+                                  s.nclients, st))
+        return rc;
+    FH_LAUNCH_CHECK(name);
+    return FH_OK;
+}
+
+// the fields every direct 3x3 WGRAD launch shares; the output (slab or dW / db) is the caller's
+static DWArgs make_dwargs(const float* x, int64_t x_cs, const float* dy, int64_t dy_cs,
+                          const int32_t* counts, int batch, int cin, int cout, int splits,
+                          int sps) {
+    DWArgs d{};
+    d.x = x; d.dy = dy; d.x_cs = x_cs; d.dy_cs = dy_cs; d.counts = counts;
+    d.batch = batch; d.cin = cin; d.M = cout; d.N = cin * 9;
+    d.splits = splits; d.stages_per_split = sps;
+    return d;
+}
+
+// ---- WGRAD routing ------------------------------------------------------------
+// From the layer's shape to the direct kernel that may run it and that kernel's plan.  The
+// launch (conv2d_wgrad_impl) and the size query (fh_conv2d_wgrad_workspace) both start here;
+// what only the launch knows — pointer alignment, a BatchNorm affine on load — is decided
+// there.  A new WGRAD kernel is one arm, one predicate here and one case there.
+enum class WArm { IGEMM, C1_MFMA, C1, SMALL, QUAD, S2 };
+struct WRoute {
+    WArm arm;
+    DWPlan p;  // (IGEMM: unused, plan_wgrad)
+};
+static WRoute wgrad_route(int cin, int cout, int h, int w, int kh, int kw, int stride, int pad,
+                          int batch, int nclients) {
+    if (conv_c1_supported(cin, cout, kh, kw, stride, pad))
+        return conv_c1_mfma_ok(h, w) ? WRoute{WArm::C1_MFMA, plan_c1_mfma(batch, h, nclients)}
+                                     : WRoute{WArm::C1, plan_c1(batch, h, w)};
+    if (dwgrad_small_supported(cin, cout, h, w, kh, kw, stride, pad))
+        return {WArm::SMALL, plan_dwgrad_small(cout, batch, w, nclients)};
+    if (dwgrad_supported(cin, cout, h, w, kh, kw, stride, pad))
+        return {WArm::QUAD, plan_dwq(cout, cin, batch, w, nclients)};
+    if (dwgrad_s2_supported(cin, cout, h, w, kh, kw, stride, pad))
+        return {WArm::S2, plan_dwgrad_s2(cout, cin, batch, /*output width*/ w / 2, nclients)};
+    return {WArm::IGEMM, DWPlan{}};
 }
 
 }  // namespace fh
@@ -2303,11 +2383,11 @@ static int conv2d_fwd_impl(const float* x, int64_t x_cs, const float* in_scale,
     if (nclients == 0) return FH_OK;
     FH_REQUIRE(x && w && y, "conv2d_fwd: null pointer");
     FH_REQUIRE((in_scale == nullptr) == (in_shift == nullptr), "conv2d_fwd: scale/shift pair");
+    DConvArgs d{};  // what the direct kernels share
+    d.in = x; d.wt = w; d.bias = bias; d.out = y;
+    d.in_cs = x_cs; d.w_cs = w_cs; d.b_cs = b_cs; d.out_cs = y_cs;
+    d.counts = counts; d.batch = batch; d.Cr = cin; d.M = cout; d.relu = relu;
     if (dconv_supported(h, w_, kh, kw, stride, pad)) {
-        DConvArgs d{};
-        d.in = x; d.wt = w; d.bias = bias; d.out = y;
-        d.in_cs = x_cs; d.w_cs = w_cs; d.b_cs = b_cs; d.out_cs = y_cs;
-        d.counts = counts; d.batch = batch; d.Cr = cin; d.M = cout; d.relu = relu;
         d.in_scale = in_scale; d.in_shift = in_shift; d.aff_cs = aff_cs;
         d.bn_part = bn_part; d.bn_tiles = (int)ceil_div((int64_t)batch * h * w_, 256);
         return run_dconv<OP_FWD>(d, w_, nclients, workspace, ws_bytes, h * w_, as_stream(stream),
@@ -2326,19 +2406,11 @@ static int conv2d_fwd_impl(const float* x, int64_t x_cs, const float* in_scale,
         return FH_OK;
     }
     if (!in_scale && !bn_part && dconv_s2_supported(h, w_, kh, kw, stride, pad)) {
-        DConvArgs d{};
-        d.in = x; d.wt = w; d.bias = bias; d.out = y;
-        d.in_cs = x_cs; d.w_cs = w_cs; d.b_cs = b_cs; d.out_cs = y_cs;
-        d.counts = counts; d.batch = batch; d.Cr = cin; d.M = cout; d.relu = relu;
         return run_dconv<OP_FWD, 2>(d, ow, nclients, workspace, ws_bytes, oh * ow,
                                     as_stream(stream), "conv2d_fwd_s2");
     }
     if (!in_scale && !bn_part && pw_s2_supported(h, w_, kh, kw, stride, pad, cin) &&
         (uintptr_t)x % 16 == 0 && x_cs % 4 == 0 && (uintptr_t)w % 16 == 0 && w_cs % 4 == 0) {
-        DConvArgs d{};
-        d.in = x; d.wt = w; d.bias = bias; d.out = y;
-        d.in_cs = x_cs; d.w_cs = w_cs; d.b_cs = b_cs; d.out_cs = y_cs;
-        d.counts = counts; d.batch = batch; d.Cr = cin; d.M = cout; d.relu = relu;
         dim3 grid((unsigned)ceil_div((int64_t)batch * oh * ow, 256), (unsigned)ceil_div(cout, 64),
                   (unsigned)nclients);
         hipStream_t st = as_stream(stream);
@@ -2665,14 +2737,13 @@ static int c1_pool_wgrad_impl(const float* x, int64_t x_cs, const float* dpool, 
     if (nclients == 0) return FH_OK;
     FH_REQUIRE(x && dpool && idx && y && dw, "conv2d_c1_pool_wgrad: null pointer");
     const bool mfma = conv_c1_mfma_ok(h, w_) && (uintptr_t)x % 16 == 0 && x_cs % 4 == 0;
-    DWPlan p{1, 1, 1, 1, conv_c1_chunks(batch, h, w_), 1};
-    if (mfma) p = plan_c1_mfma(batch, h, nclients);
-    const size_t need = dwgrad_ws_bytes(p, nclients, cout, 9);
+    const DWPlan p = mfma ? plan_c1_mfma(batch, h, nclients) : plan_c1(batch, h, w_);
+    const WSlab slab(nclients, p.splits, cout * 9, cout, workspace, db != nullptr);
+    const size_t need = slab.bytes;
     FH_REQUIRE(workspace && ws_bytes >= need, "conv2d_c1_pool_wgrad: workspace %zu < %zu",
                ws_bytes, need);
-    float* part = (float*)workspace;
-    const size_t wbytes = ((size_t)nclients * p.splits * cout * 9 * sizeof(float) + 255) / 256 * 256;
-    float* bpart = db ? (float*)((char*)workspace + wbytes) : nullptr;
+    float* part = slab.part;
+    float* bpart = slab.bias_part;
     hipStream_t st = as_stream(stream);
     // a deferred DGRAD reduction of dpool (fh_conv_defer_dgrad): summed while staging, unless
     // this launch's own partial output would overlap the slab being read
@@ -2701,30 +2772,15 @@ static int c1_pool_wgrad_impl(const float* x, int64_t x_cs, const float* dpool, 
                       dp_cs, part, bpart, counts, batch, h, w_, p.splits, p.sps, idx, i_cs, y,
                       y_cs, gh, gw, NormTail{}, DgradParts{});
         FH_LAUNCH_CHECK("conv2d_c1_pool_wgrad mfma");
-        if (defer_splits) {  // the optimizer step sums the chunks (fh_sgd_step_slabs)
-            *defer_splits = p.splits;
-            *defer_boff = wslab_bias_off(nclients, p.splits, cout * 9);
-            return FH_OK;
-        }
-        if (const int _r = splitk_sum((const float*)part, dw, dw_cs, p.splits, cout * 9,
-                                      (const float*)bpart, db, db_cs, cout, nclients, st))
-            return _r;
-        FH_LAUNCH_CHECK("conv2d_c1_pool_wgrad reduce");
-        return FH_OK;
+    } else {
+        FH_LAUNCH(conv_c1_wgrad_kernel<true>,
+                  dim3((unsigned)p.splits, (unsigned)(cout / 8), nclients), dim3(256), 0, st, x,
+                  x_cs, dpool, dp_cs, part, bpart, counts, batch, h, w_, cout, p.splits, idx, i_cs,
+                  y, y_cs, gh, gw);
+        FH_LAUNCH_CHECK("conv2d_c1_pool_wgrad");
     }
-    FH_LAUNCH(conv_c1_wgrad_kernel<true>, dim3((unsigned)p.splits, (unsigned)(cout / 8), nclients),
-              dim3(256), 0, st, x, x_cs, dpool, dp_cs, part, bpart, counts, batch, h, w_, cout,
-              p.splits, idx, i_cs, y, y_cs, gh, gw);
-    FH_LAUNCH_CHECK("conv2d_c1_pool_wgrad");
-    const int MN = cout * 9;
-    if (defer_splits) {
-        *defer_splits = p.splits;
-        *defer_boff = wslab_bias_off(nclients, p.splits, MN);
-        return FH_OK;
-    }
-    if (const int _r = splitk_sum((const float*)part, dw, dw_cs, p.splits, MN, (const float*)bpart, db, db_cs, cout, nclients, st)) return _r;
-    FH_LAUNCH_CHECK("conv2d_c1_pool_wgrad reduce");
-    return FH_OK;
+    return wgrad_finish(slab, dw, dw_cs, db, db_cs, st, defer_splits, defer_boff,
+                        "conv2d_c1_pool_wgrad reduce");
 }
 
 extern "C" int fh_conv2d_c1_pool_wgrad(const float* x, int64_t x_cs, const float* dpool,
@@ -2756,22 +2812,13 @@ extern "C" size_t fh_conv2d_wgrad_workspace(int32_t nclients, int32_t batch, int
                                             int32_t stride, int32_t pad) {
     int oh = (h + 2 * pad - kh) / stride + 1, ow = (w_ + 2 * pad - kw) / stride + 1;
     if (oh <= 0 || ow <= 0 || nclients <= 0) return 0;
-    size_t direct = 0;
-    if (dwgrad_supported(cin, cout, h, w_, kh, kw, stride, pad))  // (misaligned data: igemm)
-        direct = dwgrad_ws_bytes(plan_dwq(cout, cin, batch, w_, nclients), nclients, cout,
-                                 cin * 9);
-    if (dwgrad_small_supported(cin, cout, h, w_, kh, kw, stride, pad))
-        direct = dwgrad_ws_bytes(plan_dwgrad_small(cout, batch, w_, nclients), nclients, cout, cin * 9);
-    if (dwgrad_s2_supported(cin, cout, h, w_, kh, kw, stride, pad))
-        direct = dwgrad_ws_bytes(plan_dwgrad_s2(cout, cin, batch, ow, nclients), nclients, cout,
-                                 cin * 9);
-    if (conv_c1_supported(cin, cout, kh, kw, stride, pad)) {
-        DWPlan p{1, 1, 1, 1, conv_c1_chunks(batch, h, w_), 1};  // (also the fused-pool form)
-        direct = dwgrad_ws_bytes(p, nclients, cout, 9);
-        if (conv_c1_mfma_ok(h, w_))
-            direct = std::max(direct, dwgrad_ws_bytes(plan_c1_mfma(batch, h, nclients), nclients,
-                                                      cout, 9));
-    }
+    // the larger of the direct candidate's slab (a one-split quadrant plan, which launches
+    // without a slab, counted too) and the implicit GEMM's, which misaligned data falls back to
+    const WRoute r = wgrad_route(cin, cout, h, w_, kh, kw, stride, pad, batch, nclients);
+    const int MN = cout * cin * kh * kw;
+    size_t direct = r.arm == WArm::IGEMM ? 0 : WSlab(nclients, r.p.splits, MN, cout).bytes;
+    if (r.arm == WArm::C1_MFMA)  // misaligned x / dy: the scalar kernel (also the fused-pool form)
+        direct = std::max(direct, WSlab(nclients, plan_c1(batch, h, w_).splits, MN, cout).bytes);
     return std::max(direct, wgrad_ws_bytes(plan_wgrad(cout, cin * kh * kw, batch * oh * ow, nclients),
                                            nclients));
 }
@@ -2804,131 +2851,111 @@ static int conv2d_wgrad_impl(const float* x, int64_t x_cs, const float* in_scale
     a.M = cout; a.N = cin * kh * kw; a.K = batch * oh * ow;
     const bool aligned = ((uintptr_t)x % 16 == 0) && ((uintptr_t)dy % 16 == 0) && x_cs % 4 == 0 &&
                          dy_cs % 4 == 0;
+    // The direct candidate of this shape, then what only the launch knows: the scalar
+    // single-channel kernel takes any alignment; every other direct kernel needs 16-byte
+    // aligned x / dy, and misaligned data goes to the implicit GEMM.
+    WRoute r = wgrad_route(cin, cout, h, w_, kh, kw, stride, pad, batch, nclients);
+    const bool c1 = r.arm == WArm::C1_MFMA || r.arm == WArm::C1;
+    if (!aligned) r = c1 ? WRoute{WArm::C1, plan_c1(batch, h, w_)} : WRoute{WArm::IGEMM, DWPlan{}};
+    const DWPlan& p = r.p;
     // an armed pooled dY (fh_conv_pooled_dy) travels with a held 16x16 launch into the dual-role
     // grid; any other path reads dy, which is filled first
     bool pdy_hold = false;
     if (g_pdy.on && !g_pdy.done) {
-        if (pair && !in_scale && aligned && w_ == 16 &&
-            dwgrad_supported(cin, cout, h, w_, kh, kw, stride, pad)) {
-            const DWPlan pq = plan_dwq(cout, cin, batch, w_, nclients);
-            pdy_hold = pq.sr * w_ != 64 && (pq.splits == 1 || defer_splits);
-        }
+        if (pair && !in_scale && w_ == 16 && r.arm == WArm::QUAD)
+            pdy_hold = p.sr * w_ != 64 && (p.splits == 1 || defer_splits);
         if (!pdy_hold) {
             rc = pdy_materialize(const_cast<float*>(dy), dy_cs, counts, nclients, batch, cout, w_,
                                  as_stream(stream));
             if (rc) return rc;
         }
     }
-    if (in_scale && !(aligned && dwgrad_supported(cin, cout, h, w_, kh, kw, stride, pad))) {
+    if (in_scale && r.arm != WArm::QUAD) {
         set_error("conv2d_wgrad_bnrelu: needs the direct 3x3 wgrad (16-B aligned, channels %% 32)");
         return FH_E_UNSUPPORTED;
     }
-    if (!in_scale && conv_c1_supported(cin, cout, kh, kw, stride, pad) && conv_c1_mfma_ok(h, w_) &&
-        ((uintptr_t)x % 16 == 0) && ((uintptr_t)dy % 16 == 0) && x_cs % 4 == 0 && dy_cs % 4 == 0) {
-        const DWPlan p = plan_c1_mfma(batch, h, nclients);
-        const size_t need = dwgrad_ws_bytes(p, nclients, cout, 9);
-        FH_REQUIRE(workspace && ws_bytes >= need, "conv2d_wgrad: workspace %zu < %zu", ws_bytes,
-                   need);
-        float* part = (float*)workspace;
-        const size_t wbytes = ((size_t)nclients * p.splits * cout * 9 * sizeof(float) + 255) / 256 * 256;
-        float* bpart = db ? (float*)((char*)workspace + wbytes) : nullptr;
-        hipStream_t st = as_stream(stream);
+    hipStream_t st = as_stream(stream);
+    const int MN = a.M * a.N;
+    if (r.arm == WArm::IGEMM) {
+        const Plan g = plan_wgrad(a.M, a.N, a.K, nclients);
+        const size_t need = wgrad_ws_bytes(g, nclients);
+        FH_REQUIRE(ws_bytes >= need, "conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
+        const WSlab slab(nclients, g.splits, MN, a.M, workspace, db != nullptr);
+        a.splits = g.splits;
+        a.kchunk = g.kchunk;
+        if (g.splits == 1) {  // one K pass per tile: the kernel writes dW / db directly
+            a.out = dw;
+            a.out_cs = dw_cs;
+            a.bias_part = db;
+            a.b_cs = db_cs;
+        } else {
+            a.out = slab.part;
+            a.bias_part = slab.bias_part;
+        }
+        dim3 grid((unsigned)ceil_div(a.N, g.t.bn), (unsigned)ceil_div(a.M, g.t.bm),
+                  (unsigned)(nclients * g.splits));
+        rc = launch_shape<OP_WGRAD>(kh, kw, stride, g.t, grid, a, st);
+        if (rc) return rc;
+        FH_LAUNCH_CHECK("conv2d_wgrad");
+        if (g.splits == 1) return FH_OK;
+        return wgrad_finish(slab, dw, dw_cs, db, db_cs, st, defer_splits, defer_boff,
+                            "conv2d_wgrad reduce");
+    }
+    // The direct arms.  All write the slab, but a quadrant plan of one split per tile, whose
+    // kernel writes dW / db itself.  The single-channel arms also refuse a null workspace (as
+    // their fused-pool form, c1_pool_wgrad_impl, does); the others trust ws_bytes, which a
+    // caller without a buffer passes as 0.
+    const bool in_place = r.arm == WArm::QUAD && p.splits == 1;
+    const WSlab slab(nclients, p.splits, MN, a.M, in_place ? nullptr : workspace, db != nullptr);
+    if (!in_place) {
+        FH_REQUIRE((workspace || !c1) && ws_bytes >= slab.bytes,
+                   "conv2d_wgrad: workspace %zu < %zu", ws_bytes, slab.bytes);
+    }
+    const char* reduce = "conv2d_wgrad reduce";  // the reduction launch's label in errors
+    DWArgs d = make_dwargs(x, x_cs, dy, dy_cs, counts, batch, cin, cout, p.splits, p.sps);
+    d.part = slab.part;
+    d.bias_part = slab.bias_part;
+    switch (r.arm) {
+    case WArm::C1_MFMA: {
         const dim3 grid((unsigned)p.splits, (unsigned)nclients);
         if (cout == 32)
             FH_LAUNCH((conv_c1_wgrad_mfma_kernel<32, false>), grid, dim3(256), 0, st, x, x_cs, dy,
-                      dy_cs, part, bpart, counts, batch, h, w_, p.splits, p.sps,
+                      dy_cs, slab.part, slab.bias_part, counts, batch, h, w_, p.splits, p.sps,
                       (const uint8_t*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0, 0, 0,
                       NormTail{}, DgradParts{});
         else
             FH_LAUNCH((conv_c1_wgrad_mfma_kernel<64, false>), grid, dim3(256), 0, st, x, x_cs, dy,
-                      dy_cs, part, bpart, counts, batch, h, w_, p.splits, p.sps,
+                      dy_cs, slab.part, slab.bias_part, counts, batch, h, w_, p.splits, p.sps,
                       (const uint8_t*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0, 0, 0,
                       NormTail{}, DgradParts{});
         FH_LAUNCH_CHECK("conv2d_wgrad c1 mfma");
-        if (defer_splits) {
-            *defer_splits = p.splits;
-            *defer_boff = wslab_bias_off(nclients, p.splits, cout * cin * kh * kw);
-            return FH_OK;
-        }
-        if (const int _r = splitk_sum((const float*)part, dw, dw_cs, p.splits, cout * 9,
-                                      (const float*)bpart, db, db_cs, cout, nclients, st))
-            return _r;
-        FH_LAUNCH_CHECK("conv2d_wgrad c1 reduce");
-        return FH_OK;
+        reduce = "conv2d_wgrad c1 reduce";
+        break;
     }
-    if (!in_scale && conv_c1_supported(cin, cout, kh, kw, stride, pad)) {
-        DWPlan p{1, 1, 1, 1, conv_c1_chunks(batch, h, w_), 1};
-        const size_t need = dwgrad_ws_bytes(p, nclients, cout, 9);
-        FH_REQUIRE(workspace && ws_bytes >= need, "conv2d_wgrad: workspace %zu < %zu", ws_bytes,
-                   need);
-        float* part = (float*)workspace;
-        const size_t wbytes = ((size_t)nclients * p.splits * cout * 9 * sizeof(float) + 255) / 256 * 256;
-        float* bpart = db ? (float*)((char*)workspace + wbytes) : nullptr;
-        hipStream_t st = as_stream(stream);
+    case WArm::C1:
         FH_LAUNCH(conv_c1_wgrad_kernel<false>,
                   dim3((unsigned)p.splits, (unsigned)(cout / 8), nclients), dim3(256), 0, st, x,
-                  x_cs, dy, dy_cs, part, bpart, counts, batch, h, w_, cout, p.splits,
+                  x_cs, dy, dy_cs, slab.part, slab.bias_part, counts, batch, h, w_, cout, p.splits,
                   (const uint8_t*)nullptr, (int64_t)0, (const float*)nullptr, (int64_t)0, 0, 0);
         FH_LAUNCH_CHECK("conv2d_wgrad c1");
-        const int MN = cout * 9;
-        if (defer_splits) {
-            *defer_splits = p.splits;
-            *defer_boff = wslab_bias_off(nclients, p.splits, cout * cin * kh * kw);
-            return FH_OK;
-        }
-        if (const int _r = splitk_sum((const float*)part, dw, dw_cs, p.splits, MN, (const float*)bpart, db, db_cs, cout, nclients, st)) return _r;
-        FH_LAUNCH_CHECK("conv2d_wgrad c1 reduce");
-        return FH_OK;
-    }
-    if (aligned && dwgrad_small_supported(cin, cout, h, w_, kh, kw, stride, pad)) {
-        const DWPlan p = plan_dwgrad_small(cout, batch, w_, nclients);
-        const size_t need = dwgrad_ws_bytes(p, nclients, a.M, a.N);
-        FH_REQUIRE(ws_bytes >= need, "conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
-        DWArgs d{};
-        d.x = x; d.dy = dy; d.x_cs = x_cs; d.dy_cs = dy_cs; d.counts = counts;
-        d.batch = batch; d.cin = cin; d.M = cout; d.N = a.N;
-        d.splits = p.splits; d.stages_per_split = p.sps;
-        d.part = (float*)workspace;
-        const size_t wbytes = ((size_t)nclients * p.splits * a.M * a.N * sizeof(float) + 255) / 256 * 256;
-        d.bias_part = db ? (float*)((char*)workspace + wbytes) : nullptr;
-        hipStream_t st = as_stream(stream);
+        reduce = "conv2d_wgrad c1 reduce";
+        break;
+    case WArm::SMALL: {
         dim3 grid((unsigned)p.splits, (unsigned)(cout / 32), (unsigned)nclients);
         if (w_ == 32) FH_LAUNCH((dconv_wgrad_small_kernel<32, 3>), grid, dim3(256), 0, st, d);
         else if (w_ == 16) FH_LAUNCH((dconv_wgrad_small_kernel<16, 3>), grid, dim3(256), 0, st, d);
         else FH_LAUNCH((dconv_wgrad_small_kernel<8, 3>), grid, dim3(256), 0, st, d);
         FH_LAUNCH_CHECK("conv2d_wgrad small-cin");
-        const int MN = a.M * a.N;
-        if (defer_splits) {
-            *defer_splits = p.splits;
-            *defer_boff = wslab_bias_off(nclients, p.splits, cout * cin * kh * kw);
-            return FH_OK;
-        }
-        if (const int _r = splitk_sum((const float*)workspace, dw, dw_cs, p.splits, MN, (const float*)d.bias_part, db, db_cs, a.M, nclients, st)) return _r;
-        FH_LAUNCH_CHECK("conv2d_wgrad reduce");
-        return FH_OK;
+        break;
     }
-    if (aligned && dwgrad_supported(cin, cout, h, w_, kh, kw, stride, pad)) {
-        const DWPlan p = plan_dwq(cout, cin, batch, w_, nclients);
-        DWArgs d{};
-        d.x = x; d.dy = dy; d.x_cs = x_cs; d.dy_cs = dy_cs; d.counts = counts;
-        d.batch = batch; d.cin = cin; d.M = cout; d.N = a.N;
-        d.splits = p.splits; d.stages_per_split = p.sps;
+    case WArm::QUAD: {
         d.in_scale = in_scale; d.in_shift = in_shift; d.aff_cs = aff_cs;
-        hipStream_t st = as_stream(stream);
         dim3 grid((unsigned)p.splits, (unsigned)((cout / 32) * (cin / 32)), (unsigned)nclients);
-        if (p.splits == 1) {  // one split per tile: dW / db straight from the kernel
+        if (in_place) {
             d.dw = dw; d.dw_cs = dw_cs; d.db = db; d.db_cs = db_cs;
-        } else {
-            const size_t need = dwgrad_ws_bytes(p, nclients, a.M, a.N);
-            FH_REQUIRE(ws_bytes >= need, "conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
-            d.part = (float*)workspace;
-            const size_t wbytes = ((size_t)nclients * p.splits * a.M * a.N * sizeof(float) + 255) / 256 * 256;
-            d.bias_part = db ? (float*)((char*)workspace + wbytes) : nullptr;
         }
         if (p.sr * w_ == 64) {
-            if (w_ == 32) FH_LAUNCH((dwgrad_q_kernel<32, 64, true>), grid, dim3(256), 0, st, d);
-            else if (w_ == 16) FH_LAUNCH((dwgrad_q_kernel<16, 64, true>), grid, dim3(256), 0, st, d);
-            else FH_LAUNCH((dwgrad_q_kernel<8, 64, true>), grid, dim3(256), 0, st, d);
+            if (const int lr = launch_dwq(w_, true, d, grid, st)) return lr;
         } else if (pair && (p.splits == 1 || defer_splits)) {  // held for the next DGRAD
             if (const int fr = flush_pending_wgrad()) return fr;
             g_pend.w = w_;
@@ -2940,83 +2967,24 @@ static int conv2d_wgrad_impl(const float* x, int64_t x_cs, const float* in_scale
             g_pend.pdy = pdy_hold;
             if (pdy_hold) g_pend.d.pdy = g_pdy.p;
         } else {
-            if (w_ == 32) FH_LAUNCH((dwgrad_q_kernel<32, 128, false>), grid, dim3(256), 0, st, d);
-            else if (w_ == 16) FH_LAUNCH((dwgrad_q_kernel<16, 128, false>), grid, dim3(256), 0, st, d);
-            else FH_LAUNCH((dwgrad_q_kernel<8, 128, false>), grid, dim3(256), 0, st, d);
+            if (const int lr = launch_dwq(w_, false, d, grid, st)) return lr;
         }
         FH_LAUNCH_CHECK("conv2d_wgrad direct (quadrant waves)");
-        if (p.splits == 1) return FH_OK;
-        const int MN = a.M * a.N;
-        if (defer_splits) {
-            *defer_splits = p.splits;
-            *defer_boff = wslab_bias_off(nclients, p.splits, cout * cin * kh * kw);
-            return FH_OK;
-        }
-        if (const int _r = splitk_sum((const float*)workspace, dw, dw_cs, p.splits, MN, (const float*)d.bias_part, db, db_cs, a.M, nclients, st)) return _r;
-        FH_LAUNCH_CHECK("conv2d_wgrad reduce");
-        return FH_OK;
+        if (in_place) return FH_OK;  // defer_splits stays 0: nothing left to sum
+        break;
     }
-    if (aligned && !in_scale && dwgrad_s2_supported(cin, cout, h, w_, kh, kw, stride, pad)) {
-        const DWPlan p = plan_dwgrad_s2(cout, cin, batch, ow, nclients);
-        const size_t need = dwgrad_ws_bytes(p, nclients, a.M, a.N);
-        FH_REQUIRE(ws_bytes >= need, "conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
-        DWArgs d{};
-        d.x = x; d.dy = dy; d.x_cs = x_cs; d.dy_cs = dy_cs; d.counts = counts;
-        d.batch = batch; d.cin = cin; d.M = cout; d.N = a.N;
-        d.splits = p.splits; d.stages_per_split = p.sps;
-        d.part = (float*)workspace;
-        const size_t wbytes = ((size_t)nclients * p.splits * a.M * a.N * sizeof(float) + 255) / 256 * 256;
-        d.bias_part = db ? (float*)((char*)workspace + wbytes) : nullptr;
-        hipStream_t st = as_stream(stream);
+    case WArm::S2: {
         dim3 grid((unsigned)p.splits, (unsigned)((cout / 64) * (cin / 32)), (unsigned)nclients);
         if (ow == 16) FH_LAUNCH((dconv_wgrad_kernel<16, 2, 1, 2, 4, 2>), grid, dim3(256), 0, st, d);
         else FH_LAUNCH((dconv_wgrad_kernel<8, 2, 1, 2, 8, 2>), grid, dim3(256), 0, st, d);
         FH_LAUNCH_CHECK("conv2d_wgrad direct s2");
-        const int MN = a.M * a.N;
-        if (defer_splits) {
-            *defer_splits = p.splits;
-            *defer_boff = wslab_bias_off(nclients, p.splits, cout * cin * kh * kw);
-            return FH_OK;
-        }
-        if (const int _r = splitk_sum((const float*)workspace, dw, dw_cs, p.splits, MN, (const float*)d.bias_part, db, db_cs, a.M, nclients, st)) return _r;
-        FH_LAUNCH_CHECK("conv2d_wgrad s2 reduce");
-        return FH_OK;
+        reduce = "conv2d_wgrad s2 reduce";
+        break;
     }
-    Plan p = plan_wgrad(a.M, a.N, a.K, nclients);
-    const size_t need = wgrad_ws_bytes(p, nclients);
-    FH_REQUIRE(ws_bytes >= need, "conv2d_wgrad: workspace %zu < %zu", ws_bytes, need);
-    a.splits = p.splits;
-    a.kchunk = p.kchunk;
-    hipStream_t st = as_stream(stream);
-    if (p.splits == 1) {  // one K pass per tile: the kernel writes dW / db directly
-        a.out = dw;
-        a.out_cs = dw_cs;
-        a.bias_part = db;
-        a.b_cs = db_cs;
-        dim3 grid((unsigned)ceil_div(a.N, p.t.bn), (unsigned)ceil_div(a.M, p.t.bm),
-                  (unsigned)nclients);
-        rc = launch_shape<OP_WGRAD>(kh, kw, stride, p.t, grid, a, st);
-        if (rc) return rc;
-        FH_LAUNCH_CHECK("conv2d_wgrad");
-        return FH_OK;
+    case WArm::IGEMM:  // (ran above)
+        break;
     }
-    a.out = (float*)workspace;
-    const size_t wbytes = ((size_t)nclients * p.splits * a.M * a.N * sizeof(float) + 255) / 256 * 256;
-    a.bias_part = db ? (float*)((char*)workspace + wbytes) : nullptr;
-    dim3 grid((unsigned)ceil_div(a.N, p.t.bn), (unsigned)ceil_div(a.M, p.t.bm),
-              (unsigned)(nclients * p.splits));
-    rc = launch_shape<OP_WGRAD>(kh, kw, stride, p.t, grid, a, st);
-    if (rc) return rc;
-    FH_LAUNCH_CHECK("conv2d_wgrad");
-    const int MN = a.M * a.N;
-    if (defer_splits) {
-        *defer_splits = p.splits;
-        *defer_boff = wslab_bias_off(nclients, p.splits, cout * cin * kh * kw);
-        return FH_OK;
-    }
-    if (const int _r = splitk_sum((const float*)workspace, dw, dw_cs, p.splits, MN, (const float*)a.bias_part, db, db_cs, a.M, nclients, st)) return _r;
-    FH_LAUNCH_CHECK("conv2d_wgrad reduce");
-    return FH_OK;
+    return wgrad_finish(slab, dw, dw_cs, db, db_cs, st, defer_splits, defer_boff, reduce);
 }
 
 extern "C" int fh_conv2d_wgrad(const float* x, int64_t x_cs, const float* dy, int64_t dy_cs,
@@ -4067,8 +4035,7 @@ extern "C" int fh_conv2d_persample_sqnorm(const float* x, int64_t x_cs, const fl
 // (conv_c1_wgrad_mfma_kernel<POOLED>, seven 4-row stages = one 28x28 image per split).
 constexpr int kC1PersampleNs4Max = 512;  // image workgroups: ~two per CU
 static size_t persample_slab_bytes(int nclients, int batch, int per_w, int per_b) {
-    return (size_t)wslab_bias_off(nclients, batch, per_w) +
-           (size_t)nclients * batch * per_b * sizeof(float);
+    return WSlab(nclients, batch, per_w, per_b).bytes;
 }
 
 namespace fh {
@@ -4156,15 +4123,12 @@ extern "C" int fh_conv2d_wgrad_persample(const float* x, int64_t x_cs, const flo
                dy_cs % 4 == 0, "conv2d_wgrad_persample: x / dy must be 16-B aligned");
     const size_t need = fh_conv2d_wgrad_persample_workspace(nclients, batch, cin, cout);
     FH_REQUIRE(slab_bytes >= need, "conv2d_wgrad_persample: slab %zu < %zu", slab_bytes, need);
-    const int N = cin * 9;
-    DWArgs d{};
-    d.x = x; d.dy = dy; d.x_cs = x_cs; d.dy_cs = dy_cs; d.counts = counts;
-    d.batch = batch; d.cin = cin; d.M = cout; d.N = N;
-    d.splits = batch;                                      // one split per image
-    const int spx = w_ == 8 ? 64 : 128;                    // a stage never straddles two images
-    d.stages_per_split = (w_ * w_) / spx;
-    d.part = (float*)slab;
-    d.bias_part = (float*)((char*)slab + wslab_bias_off(nclients, batch, cout * N));
+    const int spx = w_ == 8 ? 64 : 128;  // a stage never straddles two images
+    // one split per image
+    DWArgs d = make_dwargs(x, x_cs, dy, dy_cs, counts, batch, cin, cout, batch, (w_ * w_) / spx);
+    const WSlab s(nclients, batch, cout * cin * 9, cout, slab, true);
+    d.part = s.part;
+    d.bias_part = s.bias_part;
     hipStream_t st = as_stream(stream);
     const dim3 grid((unsigned)batch, (unsigned)((cout / 32) * (cin / 32)), (unsigned)nclients);
     // fh_conv_pair armed (r05, DP-SGD's conv2): the slabs need no reduction launch, so the launch
@@ -4190,9 +4154,7 @@ extern "C" int fh_conv2d_wgrad_persample(const float* x, int64_t x_cs, const flo
         if (g_pend.pdy) g_pend.d.pdy = g_pdy.p;
         return FH_OK;
     }
-    if (w_ == 32) FH_LAUNCH((dwgrad_q_kernel<32, 128, false>), grid, dim3(256), 0, st, d);
-    else if (w_ == 16) FH_LAUNCH((dwgrad_q_kernel<16, 128, false>), grid, dim3(256), 0, st, d);
-    else FH_LAUNCH((dwgrad_q_kernel<8, 64, true>), grid, dim3(256), 0, st, d);
+    if (const int rc = launch_dwq(w_, spx == 64, d, grid, st)) return rc;
     FH_LAUNCH_CHECK("conv2d_wgrad_persample");
     return FH_OK;
 }
@@ -4212,8 +4174,9 @@ static int c1_persample_impl(const float* x, int64_t x_cs, const float* dpool, i
     const size_t need = fh_conv2d_wgrad_persample_workspace(nclients, batch, 1, cout);
     FH_REQUIRE(slab_bytes >= need, "conv2d_c1_pool_wgrad_persample: slab %zu < %zu", slab_bytes,
                need);
-    float* part = (float*)slab;
-    float* bpart = (float*)((char*)slab + wslab_bias_off(nclients, batch, cout * 9));
+    const WSlab s(nclients, batch, cout * 9, cout, slab, true);
+    float* part = s.part;
+    float* bpart = s.bias_part;
     const int sps = h / 4;  // one image per split
     const dim3 grid((unsigned)batch, (unsigned)nclients);
     hipStream_t st = as_stream(stream);

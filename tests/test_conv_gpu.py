@@ -31,6 +31,7 @@ CASES = [
     (2, 5, 32, 16, 16, 64, 3, 1, 1),
     (2, 4, 64, 8, 8, 128, 3, 1, 1),
     (2, 4, 1, 28, 28, 32, 3, 1, 1),
+    (2, 4, 1, 30, 30, 32, 3, 1, 1),  # h % 4 != 0: the scalar single-channel WGRAD kernel
     (2, 3, 32, 14, 14, 64, 3, 1, 1),
     (2, 4, 64, 16, 16, 128, 3, 2, 1),
     (2, 4, 64, 16, 16, 128, 1, 2, 0),

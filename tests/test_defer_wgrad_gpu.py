@@ -71,6 +71,7 @@ def _layer_case(n, batch, cin, h, cout, k, stride, pad, affine, bias, opt, seed=
     (5, 20, 64, 16, 64, 3, 1, 1, False, False),    # no bias (ResNet)
     (2, 32, 3, 32, 32, 3, 1, 1, False, True),      # RGB first layer (small-cin kernel)
     (3, 32, 1, 28, 32, 3, 1, 1, False, True),      # MNIST conv1 (single-channel MFMA kernel)
+    (2, 8, 1, 30, 32, 3, 1, 1, False, True),       # h % 4 != 0: single-channel scalar kernel
     (2, 32, 64, 32, 128, 3, 2, 1, False, False),   # stride-2 direct WGRAD
     (2, 32, 64, 32, 128, 1, 2, 0, False, False),   # 1x1/s2 shortcut (implicit GEMM)
     # r06: stride-2 direct WGRAD whose plan is ONE split (ResNet layer3.0.conv1 at 32 clients):
