@@ -16,7 +16,6 @@
 // Fused: the ReLU that follows BN (forward) and its mask (backward, g = dy*(y>0)),
 // and the ResNet residual add (forward) / residual-branch gradient (backward).
 #include "fh_common.h"
-#include "splitbn.h"
 
 namespace fh {
 
@@ -55,6 +54,43 @@ struct BNArgs {
     float pscale;
     int W;
     FastDiv fd_w;
+
+    // host-side fills the entry points share (bn_args() sets the shape fields)
+    void params(const float* gamma_, const float* beta_, int64_t p_cs_, float* rmean_,
+                float* rvar_, int64_t r_cs_, float* save_mean_, float* save_invstd_, float eps_,
+                float momentum_) {
+        gamma = gamma_; beta = beta_; p_cs = p_cs_;
+        rmean = rmean_; rvar = rvar_; r_cs = r_cs_;
+        save_mean = save_mean_; save_invstd = save_invstd_;
+        eps = eps_; momentum = momentum_;
+    }
+    void fwd_io(const float* x_, int64_t x_cs_, float* y_, int64_t y_cs_, const float* res_,
+                int64_t res_cs_, int relu_) {
+        x = x_; x_cs = x_cs_; y = y_; y_cs = y_cs_; res = res_; res_cs = res_cs_; relu = relu_;
+    }
+    void bwd_in(const float* x_, int64_t x_cs_, const float* gamma_, const float* beta_,
+                int64_t p_cs_, const float* save_mean_, const float* save_invstd_, int relu_) {
+        x = x_; x_cs = x_cs_; gamma = gamma_; beta = beta_; p_cs = p_cs_;
+        save_mean = (float*)save_mean_; save_invstd = (float*)save_invstd_; relu = relu_;
+    }
+    void bwd_out(float* dx_, int64_t dx_cs_, float* dgamma_, float* dbeta_, int64_t g_cs_) {
+        dx = dx_; dx_cs = dx_cs_; dgamma = dgamma_; dbeta = dbeta_; g_cs = g_cs_;
+    }
+    // the upstream gradient routed from a pooled one; its float4 path also needs W % 4 == 0
+    void pool_route(const float* dpool_, int64_t dp_cs_, const uint8_t* pidx_, int64_t pi_cs_,
+                    const uint8_t* pmask_, int64_t pm_cs_, float p_drop, int W_) {
+        dpool = dpool_; pidx = pidx_; pmask = pmask_;
+        dp_cs = dp_cs_; pi_cs = pi_cs_; pm_cs = pm_cs_;
+        pscale = 1.0f / (1.0f - p_drop);
+        W = W_;
+        fd_w = FastDiv(W_);
+        vec = (HW & 3) == 0 && (W_ & 3) == 0;
+    }
+    // partials from a convolution epilogue: one pair per 256-element tile of batch x elems
+    void conv_tiles(const double* part_, int batch_, int elems) {
+        part = (double*)part_;
+        SP = (int)ceil_div((int64_t)batch_ * elems, 256);
+    }
 };
 
 // Visit this block's slice of channel c of client z: f(offset_within_client_tensor, nvec)
@@ -125,18 +161,25 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(const BNArgs a) {
     }
 }
 
-__global__ void __launch_bounds__(256) bn_apply_kernel(const BNArgs a) {
-    const int s = blockIdx.x, c = blockIdx.y, z = blockIdx.z;
-    const int cnt = a.counts ? a.counts[z] : a.batch;
-    const int64_t n = (int64_t)cnt * a.HW;
-    double sum, sq;
-    merge(a, z, c, sum, sq);
+// The train-mode finalize of channel c of client z, the one definition every forward kernel
+// calls: the merged moments (sum, sq) over the client's n elements -> mean, clamped biased
+// variance and invstd in fp64, cast to fp32; with `write`, save_mean / save_invstd and the
+// running-statistics update (unbiased variance); returns alpha = invstd*w and
+// beta' = b - mean*alpha.  The contract: a consumer that applies the returned affine on load,
+// relu(x*scale + shift), is bit-identical to bn_apply_kernel's output, both taking alpha and
+// beta' from these operations.
+struct BNAffine {
+    float alpha, bconst;
+};
+
+__device__ __forceinline__ BNAffine bn_finalize_channel(const BNArgs& a, int z, int c, int64_t n,
+                                                        double sum, double sq, bool write) {
     const double mean = n > 0 ? sum / (double)n : 0.0;
     double var = n > 0 ? sq / (double)n - mean * mean : 0.0;
     if (var < 0.0) var = 0.0;
     const double invstd = n > 0 ? 1.0 / sqrt(var + (double)a.eps) : 0.0;
     const float meanf = (float)mean, invstdf = (float)invstd;
-    if (s == 0 && threadIdx.x == 0) {
+    if (write) {
         a.save_mean[z * a.C + c] = meanf;
         a.save_invstd[z * a.C + c] = invstdf;
         if (a.rmean && n > 0) {
@@ -147,9 +190,19 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const BNArgs a) {
             *rv = (float)((double)a.momentum * unb + (1.0 - (double)a.momentum) * (double)*rv);
         }
     }
-    // y = x*alpha + beta'  (alpha = invstd*w, beta' = b - mean*alpha), [+res], [relu]
     const float alpha = invstdf * a.gamma[z * a.p_cs + c];
-    const float bconst = a.beta[z * a.p_cs + c] - meanf * alpha;
+    return {alpha, a.beta[z * a.p_cs + c] - meanf * alpha};
+}
+
+__global__ void __launch_bounds__(256) bn_apply_kernel(const BNArgs a) {
+    const int s = blockIdx.x, c = blockIdx.y, z = blockIdx.z;
+    const int cnt = a.counts ? a.counts[z] : a.batch;
+    const int64_t n = (int64_t)cnt * a.HW;
+    double sum, sq;
+    merge(a, z, c, sum, sq);
+    // y = x*alpha + beta' [+res], [relu]
+    const BNAffine f = bn_finalize_channel(a, z, c, n, sum, sq, s == 0 && threadIdx.x == 0);
+    const float alpha = f.alpha, bconst = f.bconst;
     const float* xz = a.x + z * a.x_cs;
     float* yz = a.y + z * a.y_cs;
     const float* rz = a.res ? a.res + z * a.res_cs : nullptr;
@@ -181,8 +234,7 @@ __global__ void __launch_bounds__(256) bn_apply_kernel(const BNArgs a) {
 
 // Train-mode statistics without the apply pass: per (client, channel) the merged moments
 // become save_mean / save_invstd, the running-stat update, and the affine the consumer
-// applies on load (scale = invstd*w, shift = b - mean*scale: bn_apply_kernel's alpha and
-// beta', same operations, so relu(x*scale + shift) is bit-identical to its output).
+// applies on load (scale, shift = bn_finalize_channel's alpha, beta').
 __global__ void __launch_bounds__(256) bn_finalize_kernel(const BNArgs a, float* scale,
                                                           float* shift, int64_t s_cs) {
     // one wave per channel (merge() is wave-cooperative)
@@ -193,24 +245,9 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(const BNArgs a, float*
     double sum, sq;
     merge(a, z, c, sum, sq);
     if ((threadIdx.x & 63) != 0) return;
-    const double mean = n > 0 ? sum / (double)n : 0.0;
-    double var = n > 0 ? sq / (double)n - mean * mean : 0.0;
-    if (var < 0.0) var = 0.0;
-    const double invstd = n > 0 ? 1.0 / sqrt(var + (double)a.eps) : 0.0;
-    const float meanf = (float)mean, invstdf = (float)invstd;
-    a.save_mean[z * a.C + c] = meanf;
-    a.save_invstd[z * a.C + c] = invstdf;
-    if (a.rmean && n > 0) {
-        const double unb = n > 1 ? var * (double)n / (double)(n - 1) : var;
-        float* rm = a.rmean + z * a.r_cs + c;
-        float* rv = a.rvar + z * a.r_cs + c;
-        *rm = (float)((double)a.momentum * mean + (1.0 - (double)a.momentum) * (double)*rm);
-        *rv = (float)((double)a.momentum * unb + (1.0 - (double)a.momentum) * (double)*rv);
-    }
-    const float alpha = invstdf * a.gamma[z * a.p_cs + c];
-    const float bconst = a.beta[z * a.p_cs + c] - meanf * alpha;
-    scale[z * s_cs + c] = alpha;
-    shift[z * s_cs + c] = bconst;
+    const BNAffine f = bn_finalize_channel(a, z, c, n, sum, sq, true);
+    scale[z * s_cs + c] = f.alpha;
+    shift[z * s_cs + c] = f.bconst;
 }
 
 // BatchNorm finalize fused into the 2x2 max-pool (+dropout) that consumes the BN-ReLU output
@@ -219,8 +256,8 @@ __global__ void __launch_bounds__(256) bn_finalize_kernel(const BNArgs a, float*
 // client (BPC blocks per channel split its pooled elements); each merges the channel's
 // per-tile partials from the producing conv's epilogue (lane-strided fp64 sums combined by
 // xor-shuffles: a fixed order, the same in every block of the channel), derives the affine
-// with bn_finalize_kernel's operations, and pools relu(x*alpha + beta') exactly as
-// maxpool2_fwd_kernel (window argmax, Philox keep-mask keyed by the pooled element index).
+// (bn_finalize_channel), and pools relu(x*alpha + beta') with maxpool2_fwd_kernel's tail
+// (maxpool2_tail: window argmax, Philox keep-mask keyed by the pooled element index).
 // Block 0 of the channel writes save_mean / save_invstd, the running statistics and the
 // affine.
 constexpr int kPoolEpt = 4;  // pooled elements per thread in maxpool2_bnfin_kernel
@@ -262,27 +299,12 @@ maxpool2_bnfin_kernel(const BNArgs a, float* __restrict__ scale_out, float* __re
         double s0, s1;
         merge(a, z, c, s0, s1);
         if (lane == 0) {
-            const double mean = n > 0 ? s0 / (double)n : 0.0;
-            double var = n > 0 ? s1 / (double)n - mean * mean : 0.0;
-            if (var < 0.0) var = 0.0;
-            const double invstd = n > 0 ? 1.0 / sqrt(var + (double)a.eps) : 0.0;
-            const float meanf = (float)mean, invstdf = (float)invstd;
-            const float alpha = invstdf * a.gamma[z * a.p_cs + c];
-            const float bconst = a.beta[z * a.p_cs + c] - meanf * alpha;
-            s_aff[0] = alpha;
-            s_aff[1] = bconst;
+            const BNAffine f = bn_finalize_channel(a, z, c, n, s0, s1, sb == 0);
+            s_aff[0] = f.alpha;
+            s_aff[1] = f.bconst;
             if (sb == 0) {
-                a.save_mean[z * a.C + c] = meanf;
-                a.save_invstd[z * a.C + c] = invstdf;
-                if (a.rmean && n > 0) {
-                    const double unb = n > 1 ? var * (double)n / (double)(n - 1) : var;
-                    float* rm = a.rmean + z * a.r_cs + c;
-                    float* rv = a.rvar + z * a.r_cs + c;
-                    *rm = (float)((double)a.momentum * mean + (1.0 - (double)a.momentum) * (double)*rm);
-                    *rv = (float)((double)a.momentum * unb + (1.0 - (double)a.momentum) * (double)*rv);
-                }
-                scale_out[z * s_cs + c] = alpha;
-                shift_out[z * s_cs + c] = bconst;
+                scale_out[z * s_cs + c] = f.alpha;
+                shift_out[z * s_cs + c] = f.bconst;
             }
         }
     }
@@ -295,24 +317,8 @@ maxpool2_bnfin_kernel(const BNArgs a, float* __restrict__ scale_out, float* __re
         if (e[k] < 0) continue;
         const float v0 = fmaxf(xv[k][0] * s + t, 0.f), v1 = fmaxf(xv[k][1] * s + t, 0.f);
         const float v2 = fmaxf(xv[k][2] * s + t, 0.f), v3 = fmaxf(xv[k][3] * s + t, 0.f);
-        float m = v0;
-        int am = 0;
-        if (v1 > m) { m = v1; am = 1; }
-        if (v2 > m) { m = v2; am = 2; }
-        if (v3 > m) { m = v3; am = 3; }
-        idx[z * i_cs + e[k]] = (uint8_t)am;
-        if (drop_mode) {
-            uint8_t keep;
-            if (drop_mode == 1) {
-                const uint4 rr = Philox::gen(seed, prow, (uint64_t)e[k]);
-                keep = u01(rr.x) <= keep_prob ? 1 : 0;
-                mask[z * m_cs + e[k]] = keep;
-            } else {
-                keep = mask[z * m_cs + e[k]];
-            }
-            m = keep ? m * dscale : 0.f;
-        }
-        y[z * y_cs + e[k]] = m;
+        y[z * y_cs + e[k]] = maxpool2_tail(v0, v1, v2, v3, z, e[k], idx, i_cs, mask, m_cs, drop_mode,
+                                           keep_prob, dscale, seed, prow);
     }
 }
 
@@ -511,208 +517,6 @@ __global__ void __launch_bounds__(256) bn_bwd_apply_kernel(const BNArgs a) {
     });
 }
 
-// ---------------------------------------------------------------------------
-// r06: a split FWD conv's reduction + the BatchNorm finalize after it as one launch (splitbn.h).
-// One 1024-thread workgroup per (channel, client): its four 256-thread groups take the
-// channel's 256-element tiles in turn — the slab summed in split order, the tile's statistics
-// pair formed as splitk_epilogue_kernel forms it (wave sums, then (w0 + w1) + (w2 + w3)) — and
-// wave 0 merges the tiles as merge() does.  Everything stored is bit-identical to the
-// epilogue launch + bn_finalize / maxpool2_bnfin pair it replaces.
-constexpr int kSbnTpt = 8;  // tiles per 256-thread group in flight per pass
-// Every global load of this kernel is unconditional (indices clamped into the tensor, the
-// value discarded by a select): a load under a branch is joined by a phi whose wait drains
-// the memory pipe — one dependent round trip per load (r06 first version: 4-8 per pass).
-
-struct SbnFwd {
-    SplitBnRec r;
-    BNArgs a;  // the finalize's parameters (gamma, beta, running / saved statistics, C, HW)
-    float* scale;
-    float* shift;
-    int64_t s_cs;
-    int ntile;
-    FastDiv fd_sp;
-    // 2x2 max-pool (+ dropout) of relu(y * scale + shift): maxpool2_bnfin_kernel's outputs
-    int pool;
-    float* y;
-    int64_t y_cs;
-    uint8_t* idx;
-    int64_t i_cs;
-    uint8_t* mask;
-    int64_t m_cs;
-    int H, W, drop_mode;
-    FastDiv fd_ohw, fd_ow;
-    float keep_prob, dscale;
-    uint64_t seed_salt;
-    const uint64_t* seed_dev;
-};
-
-// Tile statistics without cross-lane trees per tile (r06 second version: 8 tiles x 2
-// xor-butterflies of ds_bpermute per thread dominated the 16x16 launches).  The epilogue's
-// tile pair is (w0 + w1) + (w2 + w3) over the tile's four 64-element chunks, each wN the
-// xor-butterfly wave_sum — whose value is the fixed tree x[i] += x[i + h], h = 32, 16, ..., 1.
-// The per-element values sit in LDS (v0; v0^2 for the second moment) and all 1024
-// threads build every chunk's tree level by level in T: the same sums in the same order.
-using SbnTree = double[2][kSbnMaxTiles * 4][16];
-
-__device__ __forceinline__ void sbn_tree(const float* v0, int nch, SbnTree& T) {
-    const int tid = threadIdx.x;
-    for (int it = tid; it < 2 * nch * 16; it += 1024) {  // levels h = 32 and 16 from LDS
-        const int st = it >= nch * 16, rem = it - st * nch * 16, ch = rem >> 4, i = rem & 15;
-        const int b = ch * 64 + i;
-        double x0 = v0[b], x1 = v0[b + 32], x2 = v0[b + 16], x3 = v0[b + 48];
-        if (st) { x0 = x0 * x0; x1 = x1 * x1; x2 = x2 * x2; x3 = x3 * x3; }
-        T[st][ch][i] = (x0 + x1) + (x2 + x3);
-    }
-#pragma unroll
-    for (int h = 8; h >= 1; h >>= 1) {
-        __syncthreads();
-        for (int it = tid; it < 2 * nch * h; it += 1024) {
-            const int st = it >= nch * h, rem = it - st * nch * h, ch = rem / h, i = rem - ch * h;
-            T[st][ch][i] = T[st][ch][i] + T[st][ch][i + h];
-        }
-    }
-    __syncthreads();
-}
-
-// the tiles' statistics pairs -> (sum0, sum1) in wave 0 (merge()'s order)
-__device__ __forceinline__ void sbn_merge(const SbnTree& T, int ntile, double& s0, double& s1) {
-    s0 = 0.0;
-    s1 = 0.0;
-    for (int i = threadIdx.x & 63; i < ntile; i += 64) {
-        s0 += (T[0][4 * i][0] + T[0][4 * i + 1][0]) + (T[0][4 * i + 2][0] + T[0][4 * i + 3][0]);
-        s1 += (T[1][4 * i][0] + T[1][4 * i + 1][0]) + (T[1][4 * i + 2][0] + T[1][4 * i + 3][0]);
-    }
-    s0 = wave_sum(s0);
-    s1 = wave_sum(s1);
-}
-
-// this thread's kSbnTpt slab values per split (clamped loads; splits <= 4)
-__device__ __forceinline__ void sbn_load_slab(const SplitBnRec& r, const float* pz, int64_t ss,
-                                              int t0, int grp, int lt, float (&v)[kSbnTpt][4]) {
-    const int nlast = (int)r.Nfull - 1, jl = r.splits - 1;
-#pragma unroll
-    for (int k = 0; k < kSbnTpt; ++k) {
-        const int nc = min((t0 + 4 * k + grp) * 256 + lt, nlast);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[k][j] = pz[min(j, jl) * ss + nc];
-    }
-}
-
-// splitk_epilogue_kernel's sum: 0 + p0 + p1 + ... in split order
-__device__ __forceinline__ float sbn_sum(const float (&v)[4], int splits) {
-    float s = 0.f;
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-        if (j < splits) s += v[j];
-    return s;
-}
-
-__global__ void __launch_bounds__(1024) split_bnfin_kernel(const SbnFwd f) {
-    __shared__ float ybuf[kSbnMaxElems];  // y, zero past the client's images
-    __shared__ SbnTree T;
-    __shared__ float s_aff[2];
-    const SplitBnRec& r = f.r;
-    const BNArgs& a = f.a;
-    const int c = blockIdx.x, z = blockIdx.y;
-    const int cnt = a.counts ? a.counts[z] : a.batch;
-    const int nvalid = cnt * r.sp;
-    const int tid = threadIdx.x, grp = tid >> 8, lt = tid & 255, lane = tid & 63;
-    const float* pz = r.part + ((int64_t)z * r.splits * r.M + c) * r.Nfull;
-    const int64_t ss = (int64_t)r.M * r.Nfull;
-    const float bv = r.bias ? r.bias[z * r.b_cs + c] : 0.f;
-    float* oz = r.out + z * r.out_cs;
-    for (int t0 = 0; t0 < f.ntile; t0 += 4 * kSbnTpt) {
-        float v[kSbnTpt][4];
-        sbn_load_slab(r, pz, ss, t0, grp, lt, v);
-#pragma unroll
-        for (int k = 0; k < kSbnTpt; ++k) {
-            const int t = t0 + 4 * k + grp;
-            if (t >= f.ntile) break;  // uniform over the 256-thread group
-            const int n = t * 256 + lt;
-            const bool ok = n < nvalid;
-            float s = sbn_sum(v[k], r.splits);
-            if (r.bias) s = s + bv;
-            if (ok) {
-                uint32_t img, pix;
-                f.fd_sp.divmod((uint32_t)n, img, pix);
-                oz[((int64_t)img * r.M + c) * r.sp + pix] = s;
-            }
-            ybuf[n] = ok ? s : 0.f;
-        }
-    }
-    __syncthreads();
-    sbn_tree(ybuf, 4 * f.ntile, T);
-    if (tid < 64) {  // bn_finalize_kernel's operations
-        double sum, sq;
-        sbn_merge(T, f.ntile, sum, sq);
-        if (lane == 0) {
-            const int64_t n = (int64_t)cnt * a.HW;
-            const double mean = n > 0 ? sum / (double)n : 0.0;
-            double var = n > 0 ? sq / (double)n - mean * mean : 0.0;
-            if (var < 0.0) var = 0.0;
-            const double invstd = n > 0 ? 1.0 / sqrt(var + (double)a.eps) : 0.0;
-            const float meanf = (float)mean, invstdf = (float)invstd;
-            a.save_mean[z * a.C + c] = meanf;
-            a.save_invstd[z * a.C + c] = invstdf;
-            if (a.rmean && n > 0) {
-                const double unb = n > 1 ? var * (double)n / (double)(n - 1) : var;
-                float* rm = a.rmean + z * a.r_cs + c;
-                float* rv = a.rvar + z * a.r_cs + c;
-                *rm = (float)((double)a.momentum * mean + (1.0 - (double)a.momentum) * (double)*rm);
-                *rv = (float)((double)a.momentum * unb + (1.0 - (double)a.momentum) * (double)*rv);
-            }
-            const float alpha = invstdf * a.gamma[z * a.p_cs + c];
-            const float bconst = a.beta[z * a.p_cs + c] - meanf * alpha;
-            f.scale[z * f.s_cs + c] = alpha;
-            f.shift[z * f.s_cs + c] = bconst;
-            s_aff[0] = alpha;
-            s_aff[1] = bconst;
-        }
-    }
-    if (!f.pool) return;  // launch-uniform
-    __syncthreads();
-    // maxpool2_bnfin_kernel's pool of relu(y * alpha + beta') from the tile values in LDS
-    const float s = s_aff[0], t = s_aff[1];
-    const int ohw = (f.H / 2) * (f.W / 2);
-    const uint64_t seed = f.seed_salt + (f.seed_dev ? *f.seed_dev : 0ull);
-    const uint64_t prow = f.drop_mode == 1 ? philox_row(f.seed_dev, z) : 0ull;
-    for (int q = tid; q < cnt * ohw; q += 1024) {
-        uint32_t img, rr, oh, ow;
-        f.fd_ohw.divmod((uint32_t)q, img, rr);
-        f.fd_ow.divmod(rr, oh, ow);
-        const int64_t e = ((int64_t)img * a.C + c) * ohw + rr;
-        const float* pp = ybuf + img * a.HW + (2 * oh) * f.W + 2 * ow;
-        const float v0 = fmaxf(pp[0] * s + t, 0.f), v1 = fmaxf(pp[1] * s + t, 0.f);
-        const float v2 = fmaxf(pp[f.W] * s + t, 0.f), v3 = fmaxf(pp[f.W + 1] * s + t, 0.f);
-        float m = v0;
-        int am = 0;
-        if (v1 > m) { m = v1; am = 1; }
-        if (v2 > m) { m = v2; am = 2; }
-        if (v3 > m) { m = v3; am = 3; }
-        f.idx[z * f.i_cs + e] = (uint8_t)am;
-        if (f.drop_mode) {
-            uint8_t keep;
-            if (f.drop_mode == 1) {
-                const uint4 rn = Philox::gen(seed, prow, (uint64_t)e);
-                keep = u01(rn.x) <= f.keep_prob ? 1 : 0;
-                f.mask[z * f.m_cs + e] = keep;
-            } else {
-                keep = f.mask[z * f.m_cs + e];
-            }
-            m = keep ? m * f.dscale : 0.f;
-        }
-        f.y[z * f.y_cs + e] = m;
-    }
-}
-
-// fused launches issued (fh_conv_bn_defer_status)
-thread_local int64_t g_sbn_taken = 0;
-
-// a pending split record nobody here consumes: launch its epilogue first
-static int sbn_settle() { return sbn_rec().pending ? sbn_materialize() : FH_OK; }
-
-int64_t sbn_taken() { return g_sbn_taken; }
-
 static void bn_geometry(int nclients, int batch, int C, int HW, int& S, int& chunk) {
     const int64_t nmax = (int64_t)batch * HW;
     int64_t want = ceil_div(2048, (int64_t)C * std::max(nclients, 1));
@@ -736,6 +540,18 @@ static BNArgs bn_args(int nclients, int batch, int C, int HW, const int32_t* cou
     return a;
 }
 
+// the backward's two passes over a.S slices (fh_bn_bwd, fh_bn_bwd_pool)
+static int bn_bwd_launch(const BNArgs& a, int nclients, void* stream, const char* reduce_name,
+                         const char* apply_name) {
+    hipStream_t st = as_stream(stream);
+    dim3 grid(a.S, a.C, nclients);
+    FH_LAUNCH(bn_bwd_reduce_kernel, grid, dim3(256), 0, st, a);
+    FH_LAUNCH_CHECK(reduce_name);
+    FH_LAUNCH(bn_bwd_apply_kernel, grid, dim3(256), 0, st, a);
+    FH_LAUNCH_CHECK(apply_name);
+    return FH_OK;
+}
+
 }  // namespace fh
 
 using namespace fh;
@@ -756,17 +572,15 @@ extern "C" int fh_bn_fwd_train(const float* x, int64_t x_cs, float* y, int64_t y
                                int32_t relu, void* workspace, size_t ws_bytes, void* stream) {
     FH_REQUIRE(nclients >= 0 && batch > 0 && C > 0 && HW > 0, "bn_fwd_train: bad shape");
     if (nclients == 0) return FH_OK;
-    if (const int rc = sbn_settle()) return rc;
     FH_REQUIRE(x && y && gamma && beta && save_mean && save_invstd, "bn_fwd_train: null pointer");
     FH_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "bn_fwd_train: running stats");
     const size_t need = fh_bn_workspace(nclients, batch, C, HW);
     FH_REQUIRE(workspace && ws_bytes >= need, "bn_fwd_train: workspace %zu < %zu", ws_bytes, need);
     BNArgs a = bn_args(nclients, batch, C, HW, counts);
-    a.x = x; a.y = y; a.res = res; a.gamma = gamma; a.beta = beta;
-    a.rmean = running_mean; a.rvar = running_var; a.save_mean = save_mean;
-    a.save_invstd = save_invstd; a.part = (double*)workspace;
-    a.x_cs = x_cs; a.y_cs = y_cs; a.res_cs = res_cs; a.p_cs = p_cs; a.r_cs = r_cs;
-    a.eps = eps; a.momentum = momentum; a.relu = relu;
+    a.fwd_io(x, x_cs, y, y_cs, res, res_cs, relu);
+    a.params(gamma, beta, p_cs, running_mean, running_var, r_cs, save_mean, save_invstd, eps,
+             momentum);
+    a.part = (double*)workspace;
     hipStream_t st = as_stream(stream);
     dim3 grid(a.S, C, nclients);
     FH_LAUNCH(bn_stats_kernel, grid, dim3(256), 0, st, a);
@@ -785,18 +599,17 @@ extern "C" int fh_bn_fwd_stats(const float* x, int64_t x_cs, const float* gamma,
                                void* workspace, size_t ws_bytes, void* stream) {
     FH_REQUIRE(nclients >= 0 && batch > 0 && C > 0 && HW > 0, "bn_fwd_stats: bad shape");
     if (nclients == 0) return FH_OK;
-    if (const int rc = sbn_settle()) return rc;
     FH_REQUIRE(x && gamma && beta && save_mean && save_invstd && scale_out && shift_out,
                "bn_fwd_stats: null pointer");
     FH_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "bn_fwd_stats: running stats");
     const size_t need = fh_bn_workspace(nclients, batch, C, HW);
     FH_REQUIRE(workspace && ws_bytes >= need, "bn_fwd_stats: workspace %zu < %zu", ws_bytes, need);
     BNArgs a = bn_args(nclients, batch, C, HW, counts);
-    a.x = x; a.gamma = gamma; a.beta = beta;
-    a.rmean = running_mean; a.rvar = running_var; a.save_mean = save_mean;
-    a.save_invstd = save_invstd; a.part = (double*)workspace;
-    a.x_cs = x_cs; a.p_cs = p_cs; a.r_cs = r_cs;
-    a.eps = eps; a.momentum = momentum;
+    a.x = x;
+    a.x_cs = x_cs;
+    a.params(gamma, beta, p_cs, running_mean, running_var, r_cs, save_mean, save_invstd, eps,
+             momentum);
+    a.part = (double*)workspace;
     hipStream_t st = as_stream(stream);
     FH_LAUNCH(bn_stats_kernel, dim3(a.S, C, nclients), dim3(256), 0, st, a);
     FH_LAUNCH_CHECK("bn_fwd_stats stats");
@@ -824,33 +637,9 @@ extern "C" int fh_bn_finalize_tiles(const double* part, const float* gamma, cons
     FH_REQUIRE((running_mean == nullptr) == (running_var == nullptr),
                "bn_finalize_tiles: running stats");
     BNArgs a = bn_args(nclients, batch, C, HW, counts);
-    a.S = a.SP = (int)ceil_div((int64_t)batch * HW, 256);
-    a.part = (double*)part;
-    a.gamma = gamma; a.beta = beta;
-    a.rmean = running_mean; a.rvar = running_var; a.save_mean = save_mean;
-    a.save_invstd = save_invstd;
-    a.p_cs = p_cs; a.r_cs = r_cs;
-    a.eps = eps; a.momentum = momentum;
-    SplitBnRec& r = sbn_rec();
-    if (r.pending) {
-        if (r.bn_part == part && r.st == as_stream(stream) && r.M == C &&
-            r.sp == HW && r.nclients == nclients && r.batch == batch && r.counts == counts) {
-            // the split conv's reduction and this finalize: one launch (splitbn.h)
-            SbnFwd f{};
-            f.r = r;
-            f.a = a;
-            f.scale = scale_out; f.shift = shift_out; f.s_cs = s_cs;
-            f.ntile = a.SP;
-            f.fd_sp = FastDiv((uint32_t)HW);
-            r.pending = false;
-            FH_LAUNCH(split_bnfin_kernel, dim3((unsigned)C, nclients), dim3(1024), 0,
-                      as_stream(stream), f);
-            FH_LAUNCH_CHECK("bn_finalize_tiles (split conv reduction)");
-            ++g_sbn_taken;
-            return FH_OK;
-        }
-        if (const int rc = sbn_materialize()) return rc;
-    }
+    a.conv_tiles(part, batch, HW);
+    a.params(gamma, beta, p_cs, running_mean, running_var, r_cs, save_mean, save_invstd, eps,
+             momentum);
     FH_LAUNCH(bn_finalize_kernel, dim3((unsigned)ceil_div(C, 4), nclients), dim3(256), 0,
               as_stream(stream), a, scale_out, shift_out, s_cs);
     FH_LAUNCH_CHECK("bn_finalize_tiles");
@@ -871,19 +660,15 @@ extern "C" int fh_bn_apply_tiles(const double* part, const float* x, int64_t x_c
                                  float eps, float momentum, int32_t relu, void* stream) {
     FH_REQUIRE(nclients >= 0 && batch > 0 && C > 0 && HW > 0, "bn_apply_tiles: bad shape");
     if (nclients == 0) return FH_OK;
-    if (const int rc = sbn_settle()) return rc;
     FH_REQUIRE(part && x && y && gamma && beta && save_mean && save_invstd,
                "bn_apply_tiles: null pointer");
     FH_REQUIRE((running_mean == nullptr) == (running_var == nullptr),
                "bn_apply_tiles: running stats");
     BNArgs a = bn_args(nclients, batch, C, HW, counts);
-    a.SP = (int)ceil_div((int64_t)batch * HW, 256);  // the conv epilogue's tiles
-    a.part = (double*)part;
-    a.x = x; a.y = y; a.res = res; a.gamma = gamma; a.beta = beta;
-    a.rmean = running_mean; a.rvar = running_var; a.save_mean = save_mean;
-    a.save_invstd = save_invstd;
-    a.x_cs = x_cs; a.y_cs = y_cs; a.res_cs = res_cs; a.p_cs = p_cs; a.r_cs = r_cs;
-    a.eps = eps; a.momentum = momentum; a.relu = relu;
+    a.conv_tiles(part, batch, HW);
+    a.fwd_io(x, x_cs, y, y_cs, res, res_cs, relu);
+    a.params(gamma, beta, p_cs, running_mean, running_var, r_cs, save_mean, save_invstd, eps,
+             momentum);
     FH_LAUNCH(bn_apply_kernel, dim3(a.S, C, nclients), dim3(256), 0, as_stream(stream), a);
     FH_LAUNCH_CHECK("bn_apply_tiles");
     return FH_OK;
@@ -909,42 +694,12 @@ extern "C" int fh_maxpool2_fwd_bnfinalize(
     FH_REQUIRE((running_mean == nullptr) == (running_var == nullptr),
                "maxpool2_fwd_bnfinalize: running stats");
     BNArgs a = bn_args(nclients, batch, C, H * W, counts);
-    a.S = a.SP = (int)ceil_div((int64_t)batch * H * W, 256);
-    a.part = (double*)part;
-    a.gamma = gamma; a.beta = beta;
-    a.rmean = running_mean; a.rvar = running_var; a.save_mean = save_mean;
-    a.save_invstd = save_invstd;
-    a.p_cs = p_cs; a.r_cs = r_cs;
-    a.eps = eps; a.momentum = momentum;
+    a.conv_tiles(part, batch, H * W);
+    a.params(gamma, beta, p_cs, running_mean, running_var, r_cs, save_mean, save_invstd, eps,
+             momentum);
     const int64_t per_ch = (int64_t)batch * (H / 2) * (W / 2);
     const int bpc = (int)std::max<int64_t>(1, ceil_div(per_ch, 256 * kPoolEpt));
     const float keep = 1.0f - p_drop;
-    SplitBnRec& r = sbn_rec();
-    if (r.pending) {
-        if (r.bn_part == part && r.st == as_stream(stream) && r.M == C &&
-            r.sp == H * W && r.out == x && r.out_cs == x_cs && r.nclients == nclients &&
-            r.batch == batch && r.counts == counts) {
-            SbnFwd f{};
-            f.r = r;
-            f.a = a;
-            f.scale = scale_out; f.shift = shift_out; f.s_cs = s_cs;
-            f.ntile = a.SP;
-            f.pool = 1;
-            f.y = y; f.y_cs = y_cs; f.idx = idx; f.i_cs = i_cs; f.mask = mask; f.m_cs = m_cs;
-            f.H = H; f.W = W; f.drop_mode = drop_mode; f.keep_prob = keep; f.dscale = 1.0f / keep;
-            f.seed_salt = seed; f.seed_dev = seed_dev;
-            f.fd_sp = FastDiv((uint32_t)(H * W));
-            f.fd_ohw = FastDiv((uint32_t)((H / 2) * (W / 2)));
-            f.fd_ow = FastDiv((uint32_t)(W / 2));
-            r.pending = false;
-            FH_LAUNCH(split_bnfin_kernel, dim3((unsigned)C, nclients), dim3(1024), 0,
-                      as_stream(stream), f);
-            FH_LAUNCH_CHECK("maxpool2_fwd_bnfinalize (split conv reduction)");
-            ++g_sbn_taken;
-            return FH_OK;
-        }
-        if (const int rc = sbn_materialize()) return rc;
-    }
     FH_LAUNCH(maxpool2_bnfin_kernel, dim3((unsigned)(C * bpc), nclients), dim3(256), 0,
               as_stream(stream), a, scale_out, shift_out, s_cs, x, x_cs, y, y_cs, idx, i_cs,
               mask, m_cs, H, W, drop_mode, keep, 1.0f / keep, seed, seed_dev, bpc);
@@ -960,13 +715,11 @@ extern "C" int fh_bn_fwd_eval(const float* x, int64_t x_cs, float* y, int64_t y_
                               int32_t relu, void* stream) {
     FH_REQUIRE(nclients >= 0 && batch > 0 && C > 0 && HW > 0, "bn_fwd_eval: bad shape");
     if (nclients == 0) return FH_OK;
-    if (const int rc = sbn_settle()) return rc;
     FH_REQUIRE(x && y && gamma && beta && running_mean && running_var, "bn_fwd_eval: null pointer");
     BNArgs a = bn_args(nclients, batch, C, HW, counts);
-    a.x = x; a.y = y; a.res = res; a.gamma = gamma; a.beta = beta;
-    a.rmean = (float*)running_mean; a.rvar = (float*)running_var;
-    a.x_cs = x_cs; a.y_cs = y_cs; a.res_cs = res_cs; a.p_cs = p_cs; a.r_cs = r_cs;
-    a.eps = eps; a.relu = relu;
+    a.fwd_io(x, x_cs, y, y_cs, res, res_cs, relu);
+    a.params(gamma, beta, p_cs, (float*)running_mean, (float*)running_var, r_cs, nullptr, nullptr,
+             eps, 0.f);
     FH_LAUNCH(bn_eval_kernel, dim3(a.S, C, nclients), dim3(256), 0, as_stream(stream), a);
     FH_LAUNCH_CHECK("bn_fwd_eval");
     return FH_OK;
@@ -982,25 +735,17 @@ extern "C" int fh_bn_bwd(const float* dy, int64_t dy_cs, const float* yout, int6
                          void* stream) {
     FH_REQUIRE(nclients >= 0 && batch > 0 && C > 0 && HW > 0, "bn_bwd: bad shape");
     if (nclients == 0) return FH_OK;
-    if (const int rc = sbn_settle()) return rc;
     FH_REQUIRE(dy && x && gamma && save_mean && save_invstd, "bn_bwd: null pointer");
     FH_REQUIRE(!relu || yout || beta, "bn_bwd: relu needs the forward output or beta");
     const size_t need = fh_bn_workspace(nclients, batch, C, HW);
     FH_REQUIRE(workspace && ws_bytes >= need, "bn_bwd: workspace %zu < %zu", ws_bytes, need);
     BNArgs a = bn_args(nclients, batch, C, HW, counts);
-    a.dy = dy; a.yout = yout; a.x = x; a.gamma = gamma; a.beta = beta;
-    a.save_mean = (float*)save_mean;
-    a.save_invstd = (float*)save_invstd; a.dx = dx; a.dres = dres; a.dgamma = dgamma;
-    a.dbeta = dbeta; a.part = (double*)workspace;
-    a.dy_cs = dy_cs; a.yo_cs = yo_cs; a.x_cs = x_cs; a.p_cs = p_cs; a.dx_cs = dx_cs;
-    a.dres_cs = dres_cs; a.g_cs = g_cs; a.relu = relu;
-    hipStream_t st = as_stream(stream);
-    dim3 grid(a.S, C, nclients);
-    FH_LAUNCH(bn_bwd_reduce_kernel, grid, dim3(256), 0, st, a);
-    FH_LAUNCH_CHECK("bn_bwd reduce");
-    FH_LAUNCH(bn_bwd_apply_kernel, grid, dim3(256), 0, st, a);
-    FH_LAUNCH_CHECK("bn_bwd apply");
-    return FH_OK;
+    a.dy = dy; a.dy_cs = dy_cs; a.yout = yout; a.yo_cs = yo_cs;
+    a.dres = dres; a.dres_cs = dres_cs;
+    a.bwd_in(x, x_cs, gamma, beta, p_cs, save_mean, save_invstd, relu);
+    a.bwd_out(dx, dx_cs, dgamma, dbeta, g_cs);
+    a.part = (double*)workspace;
+    return bn_bwd_launch(a, nclients, stream, "bn_bwd reduce", "bn_bwd apply");
 }
 
 // BN backward whose upstream gradient arrives through MaxPool2d(2,2) (+ the Dropout fused
@@ -1019,30 +764,18 @@ extern "C" int fh_bn_bwd_pool(const float* dpool, int64_t dp_cs, const uint8_t* 
                "bn_bwd_pool: bad shape");
     FH_REQUIRE(p_drop >= 0.f && p_drop < 1.f, "bn_bwd_pool: p=%g", p_drop);
     if (nclients == 0) return FH_OK;
-    if (const int rc = sbn_settle()) return rc;
     FH_REQUIRE(dpool && pidx && x && gamma && save_mean && save_invstd, "bn_bwd_pool: null pointer");
     FH_REQUIRE(!relu || yout || beta, "bn_bwd_pool: relu needs the forward output or beta");
     const int HW = H * W;
     const size_t need = fh_bn_workspace(nclients, batch, C, HW);
     FH_REQUIRE(workspace && ws_bytes >= need, "bn_bwd_pool: workspace %zu < %zu", ws_bytes, need);
     BNArgs a = bn_args(nclients, batch, C, HW, counts);
-    a.dpool = dpool; a.pidx = pidx; a.pmask = pmask;
-    a.dp_cs = dp_cs; a.pi_cs = pi_cs; a.pm_cs = pm_cs;
-    a.pscale = 1.0f / (1.0f - p_drop);
-    a.W = W;
-    a.fd_w = FastDiv(W);
-    a.vec = (HW & 3) == 0 && (W & 3) == 0;
-    a.yout = yout; a.x = x; a.gamma = gamma; a.beta = beta; a.save_mean = (float*)save_mean;
-    a.save_invstd = (float*)save_invstd; a.dx = dx; a.dgamma = dgamma; a.dbeta = dbeta;
+    a.pool_route(dpool, dp_cs, pidx, pi_cs, pmask, pm_cs, p_drop, W);
+    a.yout = yout; a.yo_cs = yo_cs;
+    a.bwd_in(x, x_cs, gamma, beta, p_cs, save_mean, save_invstd, relu);
+    a.bwd_out(dx, dx_cs, dgamma, dbeta, g_cs);
     a.part = (double*)workspace;
-    a.yo_cs = yo_cs; a.x_cs = x_cs; a.p_cs = p_cs; a.dx_cs = dx_cs; a.g_cs = g_cs; a.relu = relu;
-    hipStream_t st = as_stream(stream);
-    dim3 grid(a.S, C, nclients);
-    FH_LAUNCH(bn_bwd_reduce_kernel, grid, dim3(256), 0, st, a);
-    FH_LAUNCH_CHECK("bn_bwd_pool reduce");
-    FH_LAUNCH(bn_bwd_apply_kernel, grid, dim3(256), 0, st, a);
-    FH_LAUNCH_CHECK("bn_bwd_pool apply");
-    return FH_OK;
+    return bn_bwd_launch(a, nclients, stream, "bn_bwd_pool reduce", "bn_bwd_pool apply");
 }
 
 // BN backward from statistics a convolution's DGRAD epilogue already took
@@ -1059,14 +792,10 @@ extern "C" int fh_bn_bwd_tiles(const double* part, const float* g, int64_t g_cs_
     if (nclients == 0) return FH_OK;
     FH_REQUIRE(part && g && x && gamma && save_mean && save_invstd, "bn_bwd_tiles: null pointer");
     BNArgs a = bn_args(nclients, batch, C, HW, counts);
-    a.SP = (int)ceil_div((int64_t)batch * HW, 256);
-    a.part = (double*)part;
-    a.dy = g; a.x = x; a.gamma = gamma;
-    a.save_mean = (float*)save_mean; a.save_invstd = (float*)save_invstd;
-    a.dx = dx; a.dgamma = dgamma; a.dbeta = dbeta;
-    a.dy_cs = g_cs_; a.x_cs = x_cs; a.p_cs = p_cs; a.dx_cs = dx_cs; a.g_cs = dg_cs;
-    a.relu = 0;  // g is already masked
-    if (const int rc = sbn_settle()) return rc;
+    a.conv_tiles(part, batch, HW);
+    a.dy = g; a.dy_cs = g_cs_;
+    a.bwd_in(x, x_cs, gamma, nullptr, p_cs, save_mean, save_invstd, /*relu=*/0);  // g is masked
+    a.bwd_out(dx, dx_cs, dgamma, dbeta, dg_cs);
     FH_LAUNCH(bn_bwd_apply_kernel, dim3(a.S, C, nclients), dim3(256), 0, as_stream(stream), a);
     FH_LAUNCH_CHECK("bn_bwd_tiles");
     return FH_OK;
@@ -1091,18 +820,10 @@ extern "C" int fh_bn_bwd_pool_tiles(const double* part, const float* dpool, int6
                "bn_bwd_pool_tiles: null pointer");
     const int HW = H * W;
     BNArgs a = bn_args(nclients, batch, C, HW, counts);
-    a.SP = (int)ceil_div((int64_t)batch * (HW / 4), 256);
-    a.part = (double*)part;
-    a.dpool = dpool; a.pidx = pidx; a.pmask = pmask;
-    a.dp_cs = dp_cs; a.pi_cs = pi_cs; a.pm_cs = pm_cs;
-    a.pscale = 1.0f / (1.0f - p_drop);
-    a.W = W;
-    a.fd_w = FastDiv(W);
-    a.vec = (HW & 3) == 0 && (W & 3) == 0;
-    a.x = x; a.gamma = gamma; a.beta = beta; a.save_mean = (float*)save_mean;
-    a.save_invstd = (float*)save_invstd; a.dx = dx; a.dgamma = dgamma; a.dbeta = dbeta;
-    a.x_cs = x_cs; a.p_cs = p_cs; a.dx_cs = dx_cs; a.g_cs = g_cs; a.relu = 1;
-    if (const int rc = sbn_settle()) return rc;
+    a.conv_tiles(part, batch, HW / 4);  // the pooled grid's tiles
+    a.pool_route(dpool, dp_cs, pidx, pi_cs, pmask, pm_cs, p_drop, W);
+    a.bwd_in(x, x_cs, gamma, beta, p_cs, save_mean, save_invstd, /*relu=*/1);
+    a.bwd_out(dx, dx_cs, dgamma, dbeta, g_cs);
     FH_LAUNCH(bn_bwd_apply_kernel, dim3(a.S, C, nclients), dim3(256), 0, as_stream(stream), a);
     FH_LAUNCH_CHECK("bn_bwd_pool_tiles");
     return FH_OK;

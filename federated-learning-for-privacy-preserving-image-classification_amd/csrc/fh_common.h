@@ -229,6 +229,37 @@ __device__ __forceinline__ float u01(uint32_t x) {
     return ((float)(x >> 8) + 1.0f) * (1.0f / 16777216.0f);
 }
 
+// The tail of MaxPool2d(2,2) (+ the Dropout fused after it) for pooled element e of client z
+// (e indexes the dense [img][C][H/2][W/2] idx / mask tensors): the first maximum of the window
+// (v0 v1 / v2 v3) and its argmax byte, then drop_mode 0: no dropout; 1: draw the keep-mask
+// (Philox keyed by (seed, prow, e)) and store it; 2: read the caller's mask.  Returns the value
+// to store, max * scale where kept.  seed / prow are read once by the caller, ahead of its
+// element loop (read per element, every keep-mask byte store would force their reload).
+__device__ __forceinline__ float maxpool2_tail(float v0, float v1, float v2, float v3, int z,
+                                               int64_t e, uint8_t* idx, int64_t i_cs,
+                                               uint8_t* mask, int64_t m_cs, int drop_mode,
+                                               float keep_prob, float scale, uint64_t seed,
+                                               uint64_t prow) {
+    float m = v0;
+    int am = 0;
+    if (v1 > m) { m = v1; am = 1; }
+    if (v2 > m) { m = v2; am = 2; }
+    if (v3 > m) { m = v3; am = 3; }
+    idx[z * i_cs + e] = (uint8_t)am;
+    if (drop_mode) {
+        uint8_t keep;
+        if (drop_mode == 1) {
+            const uint4 r = Philox::gen(seed, prow, (uint64_t)e);
+            keep = u01(r.x) <= keep_prob ? 1 : 0;
+            mask[z * m_cs + e] = keep;
+        } else {
+            keep = mask[z * m_cs + e];
+        }
+        m = keep ? m * scale : 0.f;
+    }
+    return m;
+}
+
 // four N(0,1) draws (Box-Muller on one Philox block)
 __device__ __forceinline__ void gauss4(uint64_t seed, uint64_t hi, uint64_t lo, float g[4]) {
     const uint4 r = Philox::gen(seed, hi, lo);

@@ -59,24 +59,9 @@ maxpool2_fwd_kernel(const float* __restrict__ x, int64_t x_cs, float* __restrict
             v2 = fmaxf(v2 * s + t, 0.f);
             v3 = fmaxf(v3 * s + t, 0.f);
         }
-        float m = v0;
-        int a = 0;
-        if (v1 > m) { m = v1; a = 1; }
-        if (v2 > m) { m = v2; a = 2; }
-        if (v3 > m) { m = v3; a = 3; }
-        idx[z * i_cs + e] = (uint8_t)a;
-        if (drop_mode) {
-            uint8_t keep;
-            if (drop_mode == 1) {
-                const uint4 r = Philox::gen(seed, prow, (uint64_t)e);
-                keep = u01(r.x) <= keep_prob ? 1 : 0;
-                mask[z * m_cs + e] = keep;
-            } else {
-                keep = mask[z * m_cs + e];
-            }
-            m = keep ? m * scale : 0.f;
-        }
-        y[z * y_cs + (int64_t)plane * yh * yw + oh * yw + ow] = m;
+        y[z * y_cs + (int64_t)plane * yh * yw + oh * yw + ow] =
+            maxpool2_tail(v0, v1, v2, v3, z, e, idx, i_cs, mask, m_cs, drop_mode, keep_prob, scale,
+                          seed, prow);
     }
 }
 

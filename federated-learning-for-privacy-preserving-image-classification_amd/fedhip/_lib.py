@@ -181,8 +181,6 @@ SIGNATURES = {
     "fh_conv_pair_status": (I32, [P, P]),
     "fh_conv_defer_dgrad": (I32, [I32]),
     "fh_conv_defer_status": (I32, [P, P]),
-    "fh_conv_bn_defer": (I32, [I32]),
-    "fh_conv_bn_defer_status": (I32, [P, P]),
     "fh_conv_pooled_dy": (I32, [P, I64, P, I64, P, I64, I32]),
     "fh_launch_ts_set": (I32, [P, P, ctypes.c_uint32, I32, I32, I32]),
     "fh_wall_clock_khz": (I32, [P]),

@@ -604,7 +604,6 @@ class PackedNet:
             part = None
             if fuse and self.bn_epilogue:
                 part = self._bn_part(bn, co, hw)
-                ops.conv_bn_defer()  # a split plan's reduction joins the BN finalize below
             ops.conv2d_fwd(xin, W(P_, f"{cv}.weight"), W(P_, f"{cv}.bias"), c, n, B, ci, hw, hw, co,
                            3, 1, 1, counts=cnt, in_affine=aff, bn_stats=part)
             pooled = i % 2 == 1
@@ -807,8 +806,6 @@ class PackedNet:
             a = A(f"{pf}.a", co, ho, ho)
             bb, out = A(f"{pf}.b", co, ho, ho), A(f"{pf}.out", co, ho, ho)
             p1 = self._bn_part(f"{pf}.bn1", co, ho) if epi and s == 1 else None
-            if p1 is not None:
-                ops.conv_bn_defer()  # a split plan's reduction joins bn1's finalize
             ops.conv2d_fwd(xin, W(P_, f"{pf}.conv1.weight"), None, a, n, B, ci, hi, hi, co, 3, s, 1,
                            counts=cnt, bn_stats=p1)
             if fuse:

@@ -1189,22 +1189,6 @@ int fh_conv_defer_dgrad(int32_t on);
 /* r06 (instrumentation): DGRADs the calling thread left unreduced under fh_conv_defer_dgrad, and
  * how many of those partial slabs a conv1 weight-gradient consumer summed while staging. */
 int fh_conv_defer_status(int64_t* deferred, int64_t* taken);
-/* r06: fh_conv_bn_defer(max_elems) arms the calling thread's next fh_conv2d_fwd_bnstats call:
- * when it plans a split direct launch (at most 4 splits, batch x plane <= min(max_elems, 8192)),
- * its split reduction — the splitk_epilogue launch that writes the output and the statistics
- * tiles — is left to the BatchNorm call that consumes those tiles, which the caller issues
- * next: fh_bn_finalize_tiles or fh_maxpool2_fwd_bnfinalize.  That call then runs the reduction
- * and its own pass as ONE launch (one workgroup per channel and client), every stored value
- * bit-identical to the two launches.  Until then the conv's output is unwritten: only another
- * direct-conv or fh_bn_* call that finds the reduction pending launches it first, no other
- * library call does; fh_conv_pair(-1) drops it.  max_elems 0 disarms.
- * Measured no faster than the two launches on MI355X (fedhip.ops.SPLIT_BN: off by default).
- * Replaces nothing in the reference: the pair is BatchNorm2d after Conv2d,
- * src/shared/models_pytorch.py:133-150 (CIFAR10CNN), :189-194 (FederatedResNet block). */
-int fh_conv_bn_defer(int32_t max_elems);
-/* r06 (instrumentation): split reductions the calling thread left to a BN call, and fused
- * launches the BN calls issued. */
-int fh_conv_bn_defer_status(int64_t* deferred, int64_t* taken);
 /* The next WGRAD + DGRAD pair's output gradient is a 2x2 max-pool's backward (SimpleCNN conv2,
  * models_pytorch.py:88-90, pool2 after relu(conv2)): dY(y, x) = dpool[y/2][x/2] where (y, x) is
  * the window's argmax pidx and the pooled ReLU output ypool there is > 0, else 0

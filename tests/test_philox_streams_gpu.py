@@ -10,21 +10,30 @@ asserts on every element and launches unmodified project kernels at valid argume
 
 Philox call sites in csrc/ and the test that pins each
 ------------------------------------------------------
-`Philox::gen` has eight callers:
+`Philox::gen` has six callers:
 
-  fh_common.h:212  gauss4                     through its two callers, below
+  fh_common.h:265  gauss4                     through its two callers, below
   dp.hip:107       dp_apply_kernel            test_dp_apply_* (direct)
-  layers.hip:71    maxpool2_fwd_kernel        test_maxpool_mask* (direct; dense, pitched); its
+  fh_common.h:252  maxpool2_tail, the pool + dropout tail of two kernels:
+                     maxpool2_fwd_kernel (layers.hip:63):
+                                              test_maxpool_mask* (direct; dense, pitched); its
                                               BN-on-load entry (fh_maxpool2_fwd_bnrelu) is the
                                               same kernel, tied by test_fuse_bn_gpu.py::
                                               test_fused_ops_match_apply_pass (m1 == m2)
-  layers.hip:136   dropout_fwd_kernel         test_dropout_mask* (direct)
-  layers.hip:901   gather_u8_kernel           test_gather_u8_draws* (direct); the pixels are tied
+                     maxpool2_bnfin_kernel (bn.hip:320):
+                                              test_fuse_bn_gpu.py::
+                                              test_pool_finalize_matches_separate_launches
+                                              (mask == maxpool2_fwd's), and
+                                              test_fused_pool_finalize_mask[_after_split_conv]
+                                              (direct, id block; after an unsplit and a split
+                                              conv plan)
+  layers.hip:121   dropout_fwd_kernel         test_dropout_mask* (direct)
+  layers.hip:886   gather_u8_kernel           test_gather_u8_draws* (direct); the pixels are tied
                                               to the recorded draws by the oracle test
   conv.hip:71      apply_dropout, called with a counter of its own from four FWD epilogues, all
                    reached through fh_linear_fwd_dropout:
-                     linear_fwd_skinny_kernel (conv.hip:3500) and linear_fwd_epilogue_kernel
-                     (:3538), batch <= 32:     test_classifier_gpu.py::
+                     linear_fwd_skinny_kernel (conv.hip:3465) and linear_fwd_epilogue_kernel
+                     (:3503), batch <= 32:     test_classifier_gpu.py::
                                               test_linear_fwd_dropout_equals_two_launches
                                               (mask == dropout_fwd's; its shapes all take
                                               these two), and test_fused_linear_dropout_mask
@@ -33,14 +42,6 @@ Philox call sites in csrc/ and the test that pins each
                      in_f % 32 != 0:           no equality test runs them;
                                               test_fused_linear_dropout_mask[igemm,
                                               igemm_splitk] (direct, id block)
-  bn.hip:307       maxpool2_bnfin_kernel      test_fuse_bn_gpu.py::
-                                              test_pool_finalize_matches_separate_launches
-                                              (mask == maxpool2_fwd's), and
-                                              test_fused_pool_finalize_mask (direct, id block)
-  bn.hip:696       split_bnfin_kernel         test_split_bn_gpu.py::
-                                              test_fwd_reduction_in_finalize_bitwise (mask ==
-                                              maxpool2_bnfin_kernel's), and
-                                              test_fused_split_bn_mask (direct, id block)
 
 `gauss4` has two callers:
 
@@ -439,9 +440,8 @@ def test_fused_linear_dropout_mask(nc, B, in_f, out_f):
         assert bool((err[keep] <= bound[keep]).all()), (z, float((err / bound)[keep].max()))
 
 
-def _conv_with_stats(nc, B, ci, co, hw, cd, arm=False):
-    """cd: the device counts tensor, the same object for the BN call that follows (a deferred
-    split reduction is matched to it by its pointers)."""
+def _conv_with_stats(nc, B, ci, co, hw, cd, in_affine=False):
+    """in_affine: the input is a BN pre-activation, relu(x*scale + shift) applied on load."""
     torch.manual_seed(nc * 11 + co)
     x = torch.randn(nc, B, ci, hw, hw, device=DEV)
     w = torch.randn(nc, co, ci, 3, 3, device=DEV) / (3.0 * ci ** 0.5)
@@ -449,14 +449,8 @@ def _conv_with_stats(nc, B, ci, co, hw, cd, arm=False):
     c = torch.zeros(nc, B, co, hw, hw, device=DEV)
     part = torch.zeros(nc, co, ops.bnstats_tiles(B, hw, hw), 2, dtype=torch.float64, device=DEV)
     aff = None
-    if arm:  # test_split_bn_gpu.py's call: a BN-on-load input, the reduction left to the BN call
+    if in_affine:
         aff = (torch.rand(nc, ci, device=DEV) + 0.5, torch.randn(nc, ci, device=DEV) * 0.1)
-        prev = ops.SPLIT_BN[0]
-        ops.SPLIT_BN[0] = True
-        try:
-            ops.conv_bn_defer(8192)
-        finally:
-            ops.SPLIT_BN[0] = prev
     ops.conv2d_fwd(x, w, bias, c, nc, B, ci, hw, hw, co, 3, 1, 1, counts=cd, in_affine=aff,
                    bn_stats=part)
     return c, part
@@ -489,19 +483,17 @@ def test_fused_pool_finalize_mask():
     _check_mask_rows(mb, counts, C * (hw // 2) ** 2, p, 5, blk)
 
 
-def test_fused_split_bn_mask():
-    """split_bnfin_kernel's draw: the armed split conv's reduction runs inside the pool-finalize
-    call (test_split_bn_gpu.py's smallest pooled shape), under a key block with a client id."""
+def test_fused_pool_finalize_mask_after_split_conv():
+    """maxpool2_bnfin_kernel's draw after a conv that takes a split plan (one client on the
+    whole chip: the statistics tiles come from the split reduction's epilogue), its input a BN
+    pre-activation, under a key block with a client id >= 2^32."""
     nc, B, C, hw, p = 1, 32, 64, 16, 0.3
     ops.set_fill_fraction(1.0)  # the split plan assumes the whole-chip planner
     counts = [B]
     cd = _i32(counts)
     blk, blk_t = _block(STEP_KEY, [BIG_ID])
-    d0, t0 = ops.bn_defer_status()
-    c, part = _conv_with_stats(nc, B, 64, C, hw, cd, arm=True)
+    c, part = _conv_with_stats(nc, B, 64, C, hw, cd, in_affine=True)
     mb = _pool_finalize(nc, B, C, hw, cd, c, part, p, 17, blk_t)
-    d1, t1 = ops.bn_defer_status()
-    assert d1 == d0 + 1 and t1 == t0 + 1, (d0, t0, d1, t1)  # the fused kernel really ran
     _check_mask_rows(mb, counts, C * (hw // 2) ** 2, p, 17, blk)
 
 
